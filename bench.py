@@ -12,7 +12,13 @@ Multi-GPU: inference does not shard: N ranks run N
 independent replicas of the same step; value = all output samples / the
 slowest rank's time ("scaling": "weak").
 
-Extra fields:
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, config ...); the
+legs below are None in it.  ``--dump-outputs DIR`` then writes the waveform
+the last timed step returned as DIR/wav.npy (float32; the seeded inputs and
+the key-hash weights are the same from run to run).
+
+Extra fields (``--full`` only; each has a ``--no-...`` switch):
   roofline      the dominant kernel (conv1d_mfma_kernel + the fused ResBlock2
                 pair kernel, every conv launch of the step): algorithmic FLOPs /
                 HIP-event-timed kernel time,
@@ -32,9 +38,10 @@ Extra fields:
                 scaling, value = all ranks' utterances / slowest rank's time.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
-       [--tx 100] [--ty 500] [--graph] [--no-cpu-baseline]
-       [--train-batch 32] [--train-steps 5] [--train-warmup 2] [--no-train]
-       [--no-longform]
+       [--tx 100] [--ty 500] [--graph] [--dump-outputs DIR]
+       [--full [--no-cpu-baseline] [--no-roofline] [--train-batch 32]
+        [--train-steps 5] [--train-warmup 2] [--no-train] [--no-longform]
+        [--no-kernels]]
 """
 from __future__ import annotations
 
@@ -640,6 +647,37 @@ def _guarded(name, fn, *a, **k):
         return {"error": f"{name}: {type(e).__name__}: {e}"[:400]}
 
 
+DUMP_MAX_BYTES = 64_000_000
+NPY_HEADER_BYTES = 1024  # allowance per file (a .npy header is 128 bytes here)
+
+
+def dump_outputs(dirname, outputs, rank=0, world=1):
+    """--dump-outputs: each array of ``outputs`` (what the last timed step
+    returned) as <dirname>/<name>.npy in float32 (float64 stays float64),
+    <name>_rank<r>.npy on the ranks of a multi-GPU run.  All files together,
+    headers included, stay within DUMP_MAX_BYTES: a larger output is cut to a
+    fixed sample of its flattened elements, one per equal stratum of the index
+    range at an offset drawn from a generator seeded with 0 (distinct,
+    ascending, the same for every run of the same shape)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_MAX_BYTES // (max(1, len(outputs)) * world) - NPY_HEADER_BYTES
+    for name, t in outputs.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        n, k = t.numel(), budget // t.element_size()
+        if n > k:
+            g = torch.Generator().manual_seed(0)
+            lo = torch.arange(k + 1, dtype=torch.int64) * n // k  # stratum bounds
+            width = lo[1:] - lo[:-1]
+            off = (torch.rand(k, generator=g, dtype=torch.float64) * width).long()
+            idx = lo[:-1] + torch.minimum(off, width - 1)
+            t = t.flatten()[idx.to(t.device)]
+        fn = name if world == 1 else f"{name}_rank{rank}"
+        np.save(os.path.join(dirname, fn + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -651,6 +689,11 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay a captured hipGraph per step")
     ap.add_argument("--fp32-mode", choices=("split", "exact"), default=None,
                     help="fp32 conv arithmetic (vits_amd.engine.FP32_MODE; default split)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/wav.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: train (C4, C3), roofline and "
+                         "kernel table, longform (C5), kernels, latency, CPU baselines")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--train-batch", type=int, default=32, help="C4: utterances per GPU")
@@ -666,6 +709,11 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU-only check of the rank launcher / aggregation (gloo, no GPU work)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the headline's timed steps only
+        args.no_train = args.no_roofline = args.no_longform = args.no_kernels = True
+        args.no_cpu_baseline = True
     if args.fp32_mode:  # read by vits_amd.engine at import
         os.environ["VITS_FP32_MODE"] = args.fp32_mode
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -735,6 +783,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"wav": out}, rank, world)
 
         roof = None
         kernel_table = []
@@ -820,7 +870,8 @@ def main():
         # the per-shape kernel table (long) goes on a line of its own before
         # the result line; the result line ends with the legs of the metric's
         # second half so a tail of stdout shows them
-        print("kernel_table " + json.dumps(kernel_table), flush=True)
+        if args.full:
+            print("kernel_table " + json.dumps(kernel_table), flush=True)
         line.update({"kernels": kern, "latency_b1": latency, "longform": longform,
                      "train_c3": train_c3, "train": train})
         print(json.dumps(line), flush=True)

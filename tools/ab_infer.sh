@@ -6,7 +6,7 @@ mkdir -p gpurun_out/ab
 for r in $(seq 1 "$ROUNDS"); do
   i=0
   for e in "$@"; do
-    env $e timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline \
+    env $e timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline \
       --no-train --no-longform --no-kernels > gpurun_out/ab/infer.$i.$r.json 2> gpurun_out/ab/infer.$i.$r.err || exit 1
     i=$((i+1))
   done

@@ -4,7 +4,7 @@
 # with src prefix prof_<tag>_longform).
 set -e
 TAG=${1:-r03}
-OUT=gpurun_out/prof_${TAG}_longform
+OUT=${LOGS:-bench_logs}/prof_${TAG}_longform
 export TMPDIR=/tmp
 mkdir -p $OUT
 for R in 1 2; do

@@ -4,7 +4,7 @@
 set -e
 TAG=${1:-r03}
 B=${2:-32}
-OUT=gpurun_out/prof_${TAG}_train
+OUT=${LOGS:-bench_logs}/prof_${TAG}_train
 export TMPDIR=/tmp
 mkdir -p $OUT
 # one unprofiled run first: MIOpen's exhaustive find (cudnn.benchmark, as the

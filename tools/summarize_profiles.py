@@ -18,7 +18,7 @@ import sys
 from collections import defaultdict
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
-src = os.path.join("gpurun_out", f"prof_{tag}")
+src = os.path.join(os.environ.get("LOGS", "bench_logs"), f"prof_{tag}")  # as run_profiles.sh
 dst = "profiles"
 os.makedirs(dst, exist_ok=True)
 shutil.copy(os.path.join(src, "trace", "run_kernel_stats.csv"),

@@ -16,7 +16,7 @@ from collections import defaultdict
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 32
 kind = sys.argv[3] if len(sys.argv) > 3 else "train"  # or "longform" (tools/run_longform_profiles.sh)
-src = os.path.join("gpurun_out", f"prof_{tag}_{kind}")
+src = os.path.join(os.environ.get("LOGS", "bench_logs"), f"prof_{tag}_{kind}")  # as the run_*.sh
 
 
 def family(name):
