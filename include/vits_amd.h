@@ -36,6 +36,8 @@
  *   vits_layer_norm_channels modules.LayerNorm (modules.py:41-44)
  *   vits_attention_forward   MultiHeadAttention.attention core
  *                            (attentions.py:85-100)
+ *   vits_attention_train_forward /  the same core in training, with its
+ *   vits_attention_backward         dropout (attentions.py:97) and gradients
  */
 #ifndef VITS_AMD_H
 #define VITS_AMD_H
@@ -347,6 +349,49 @@ int vits_attention_forward(const float* q, const float* k, const float* v, float
                            int batch, int heads, int head_dim, int t_len,
                            int64_t qkv_bstride, int64_t out_bstride, const int32_t* lengths,
                            void* stream);
+
+/* ---------------------------------------------------------------------- */
+/* The same attention for training (MultiHeadAttention.forward,           */
+/* attentions.py:79-100 incl. self.drop): layout, mask and padding rules  */
+/* of vits_attention_forward; q / k / v / out (and the gradients) of      */
+/* `dtype` (VITS_DT_F32: fp32 MFMA; VITS_DT_F16 / _BF16: 16-bit MFMA,     */
+/* fp32 accumulation and softmax).                                        */
+/*   lse   fp32 [B][H][T]: log-sum-exp of each query's masked scores      */
+/*         (saved for the backward)                                       */
+/*   p_drop, seed: dropout of the normalised probabilities,               */
+/*         out = (P * keep / (1 - p_drop)) V, keep a counter-based hash   */
+/*         of (*seed, b, h, query, key).  seed is a DEVICE int64 read by  */
+/*         the kernel (capture-safe); p_drop == 0 never reads it (may be  */
+/*         NULL) and computes exactly vits_attention_forward's result.    */
+/* 0 <= p_drop < 1, else VITS_E_ARG; head_dim as above, else VITS_E_UNSUP. */
+/* ---------------------------------------------------------------------- */
+int vits_attention_train_forward(const void* q, const void* k, const void* v, void* out,
+                                 float* lse, int batch, int heads, int head_dim, int t_len,
+                                 int64_t qkv_bstride, int64_t out_bstride,
+                                 const int32_t* lengths, int dtype, float p_drop,
+                                 const int64_t* seed, void* stream);
+
+/* Backward of vits_attention_train_forward: dq / dk / dv [B][H*D][T] of   */
+/* `dtype` with batch stride dqkv_bstride (e.g. the channel slices of one */
+/* [B][3C][T] gradient buffer) from q, k, v, out, dout (batch strides     */
+/* qkv_bstride / out_bstride / dout_bstride), the saved lse and the same  */
+/* p_drop / seed.  S and P are recomputed from lse; dS = P * (keep /      */
+/* (1 - p) * (dout . V) - delta), delta[q] = sum_d dout * out, and dS = 0  */
+/* wherever the score was filled with -1e4 (dv still receives those       */
+/* rows' uniform P).  Two launches, no atomics, fixed reduction order:     */
+/* dq (+ delta, an fp32 [B][H][T] workspace the caller provides) by       */
+/* query tile, then dk / dv by key tile.                                  */
+int vits_attention_backward(const void* q, const void* k, const void* v, const void* out,
+                            const void* dout, const float* lse, void* dq, void* dk, void* dv,
+                            float* delta, int batch, int heads, int head_dim, int t_len,
+                            int64_t qkv_bstride, int64_t out_bstride, int64_t dout_bstride,
+                            int64_t dqkv_bstride, const int32_t* lengths, int dtype,
+                            float p_drop, const int64_t* seed, void* stream);
+
+/* The dropout keep mask of the two calls above as uint8 [B][H][T][T]     */
+/* ([query][key]; 1 = kept) - for tests.                                  */
+int vits_attention_dropout_mask(const int64_t* seed, uint8_t* mask, int batch, int heads,
+                                int t_len, float p_drop, void* stream);
 
 /* ---------------------------------------------------------------------- */
 /* Training-step convs (backward of every stride-1 nn.Conv1d the          */
@@ -718,7 +763,8 @@ int vits_amd_device_arch(char* buf, int len);
 #define VITS_CNT_GATE_16 6       /* vits_gate_*_io16                        */
 #define VITS_CNT_RESBLOCK 7      /* vits_resblock_pair*_forward             */
 #define VITS_CNT_PACK 8          /* vits_conv1d_pack*                       */
-#define VITS_CNT_N 9
+#define VITS_CNT_ATTN 9          /* vits_attention_train_forward / _backward */
+#define VITS_CNT_N 10
 int64_t vits_dispatch_count(int which);
 void vits_dispatch_count_reset(void);
 

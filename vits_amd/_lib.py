@@ -317,6 +317,18 @@ _SIGS = {
         C.c_int,
         [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
     ),
+    "vits_attention_train_forward": (
+        C.c_int,
+        [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_float,
+                                           C.c_void_p, C.c_void_p],
+    ),
+    "vits_attention_backward": (
+        C.c_int,
+        [C.c_void_p] * 10 + [C.c_int] * 4 + [C.c_int64] * 4
+        + [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p],
+    ),
+    "vits_attention_dropout_mask": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "vits_conv1d_pack16": (
         C.c_int,
         [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 3
@@ -416,7 +428,7 @@ class VitsAmdError(RuntimeError):
 
 # vits_dispatch_count families (include/vits_amd.h VITS_CNT_*)
 CNT_NAMES = ("conv_f32", "conv_split", "conv_16", "wgrad_f32", "wgrad_16", "gate_f32",
-             "gate_16", "resblock", "pack")
+             "gate_16", "resblock", "pack", "attn")
 
 
 def dispatch_counts() -> dict:

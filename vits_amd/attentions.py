@@ -1,8 +1,11 @@
 """Post-LN transformer text encoder (reference ``attentions.py``).
 
-``forward`` is the masked training path (PyTorch-ROCm ops under autograd);
-``infer`` runs through the HIP kernels (MFMA conv projections, the fused
-flash-style attention kernel, channel LayerNorm) via ``vits_amd.engine``.
+``forward`` is the masked training path: the projections, the attention core
+(``train_ops.attention``: csrc/attention.hip's differentiable kernels, with
+dropout) and the FFN convs / gate on the HIP training kernels under
+autograd, torch for the rest; ``infer`` runs through the HIP kernels (MFMA
+conv projections, the fused flash-style attention kernel, channel LayerNorm)
+via ``vits_amd.engine``.
 """
 from __future__ import annotations
 
@@ -19,6 +22,10 @@ from .modules import LayerNorm
 # self-attention's q / k / v projections as one HIP conv under autocast
 # (train_ops.conv1d_cat); False (tests) keeps three
 QKV_CAT = True
+
+# the training attention core on the HIP kernels (train_ops.AttentionHip);
+# False (tests) keeps the reference's matmul / softmax / dropout chain on torch
+ATTN_HIP = True
 
 
 class MultiHeadAttention(nn.Module):
@@ -48,9 +55,13 @@ class MultiHeadAttention(nn.Module):
 
     def forward(self, x, c, attn_mask=None, lengths=None):
         """lengths (int [B], optional): the key / query lengths attn_mask was
-        built from (Encoder: x_mask outer product); unused in training, where
-        the attention core is the reference's batched matmul / softmax
-        (hipBLASLt; the inference plans run csrc/attention.hip instead)."""
+        built from (Encoder: x_mask outer product).  With them the attention
+        core is the differentiable HIP attention (train_ops.attention, which
+        masks by length and applies the dropout itself: attn_mask is then
+        IGNORED, so it must be the outer product of the length masks, and
+        lengths must not be passed with any other mask); without them, on
+        CPU or with ATTN_HIP off it is the reference's batched matmul /
+        masked_fill / softmax / dropout chain on torch, as in ``attention``."""
         # 1x1 projections on the HIP training conv under autocast (torch otherwise)
         conv = train_ops.conv1d
         qkv = (train_ops.conv1d_cat((self.conv_q, self.conv_k, self.conv_v), x)
@@ -59,7 +70,8 @@ class MultiHeadAttention(nn.Module):
             q, k, v = qkv
         else:
             q, k, v = conv(self.conv_q, x), conv(self.conv_k, c), conv(self.conv_v, c)
-        y = self.attention(q, k, v, mask=attn_mask)[0]
+        y = train_ops.attention(q, k, v, self.n_heads, lengths, self.p_dropout, self.training,
+                                mask=attn_mask)
         return conv(self.conv_o, y)
 
     def attention(self, query, key, value, mask=None):

@@ -1018,6 +1018,82 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n_heads: int,
 _DT = {torch.float32: _lib.DT_F32, torch.float16: _lib.DT_F16, torch.bfloat16: _lib.DT_BF16,
        torch.int32: _lib.DT_I32}
 
+ATTN_HEAD_DIMS = (16, 32, 48, 64, 96, 128)
+
+
+def _attn_layout(q, k, v):
+    B, Cc, T = q.shape
+    assert q.dtype == k.dtype == v.dtype and q.dtype in (torch.float32, torch.float16,
+                                                         torch.bfloat16), q.dtype
+    assert q.shape == k.shape == v.shape, "self-attention: equal query and key lengths"
+    assert q.stride() == k.stride() == v.stride() and q.stride(2) == 1 and q.stride(1) == T
+    return B, Cc, T
+
+
+def _attn_seed(p_drop: float, seed):
+    if p_drop > 0.0:
+        assert seed is not None and seed.dtype == torch.int64 and seed.device.type == "cuda"
+        return seed.data_ptr()
+    return None
+
+
+def attention_train_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n_heads: int,
+                            lengths: Optional[torch.Tensor] = None, p_drop: float = 0.0,
+                            seed: Optional[torch.Tensor] = None):
+    """``attention`` for training: (out, lse) with out = dropout(softmax(...), p_drop) v in
+    q's dtype (fp32 / fp16 / bf16) and lse fp32 [B, H, T], the log-sum-exp of every
+    query's masked scores.  ``seed``: int64 device tensor (1 element), read by the kernel;
+    the keep mask is ``attention_dropout_mask(seed, ...)``."""
+    require_device(q, k, v, lengths, seed)
+    B, Cc, T = _attn_layout(q, k, v)
+    out = torch.empty(B, Cc, T, device=q.device, dtype=q.dtype)
+    lse = torch.empty(B, n_heads, T, device=q.device, dtype=torch.float32)
+    check(_lib.load().vits_attention_train_forward(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), B, n_heads,
+        Cc // n_heads, T, q.stride(0), out.stride(0), _ptr(lengths), _DT[q.dtype], p_drop,
+        _attn_seed(p_drop, seed), _stream_ptr(q.device)), "vits_attention_train_forward")
+    return out, lse
+
+
+def attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor,
+                       dout: torch.Tensor, lse: torch.Tensor, n_heads: int,
+                       lengths: Optional[torch.Tensor] = None, p_drop: float = 0.0,
+                       seed: Optional[torch.Tensor] = None, grads=None):
+    """(dq, dk, dv) of ``attention_train_forward`` in q's dtype.  ``grads``: optional
+    (dq, dk, dv) tensors to write (equal strides; e.g. the channel slices of one
+    [B, 3C, T] buffer); by default the slices of one new such buffer.  Two launches,
+    no atomics: the same call twice is bit-identical."""
+    require_device(q, k, v, out, dout, lse, lengths, seed)
+    B, Cc, T = _attn_layout(q, k, v)
+    assert out.dtype == q.dtype and dout.dtype == q.dtype
+    for t in (out, dout):
+        assert t.shape == q.shape and t.stride(2) == 1 and t.stride(1) == T
+    assert lse.dtype == torch.float32 and lse.shape == (B, n_heads, T) and lse.is_contiguous()
+    if grads is None:
+        grads = torch.empty(B, 3 * Cc, T, device=q.device, dtype=q.dtype).split(Cc, 1)
+    dq, dk, dv = grads
+    for t in (dq, dk, dv):
+        assert t.shape == q.shape and t.dtype == q.dtype
+    assert dq.stride() == dk.stride() == dv.stride() and dq.stride(2) == 1 and dq.stride(1) == T
+    delta = torch.empty(B, n_heads, T, device=q.device, dtype=torch.float32)
+    check(_lib.load().vits_attention_backward(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+        dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), B, n_heads, Cc // n_heads,
+        T, q.stride(0), out.stride(0), dout.stride(0), dq.stride(0), _ptr(lengths), _DT[q.dtype],
+        p_drop, _attn_seed(p_drop, seed), _stream_ptr(q.device)), "vits_attention_backward")
+    return dq, dk, dv
+
+
+def attention_dropout_mask(seed: torch.Tensor, B: int, H: int, T: int, p: float) -> torch.Tensor:
+    """The keep mask (uint8 [B, H, T, T], [query][key], 1 = kept) the training attention
+    draws for ``seed`` at dropout probability ``p`` (tests)."""
+    require_device(seed)
+    mask = torch.empty(B, H, T, T, device=seed.device, dtype=torch.uint8)
+    check(_lib.load().vits_attention_dropout_mask(_attn_seed(p, seed), mask.data_ptr(), B, H, T, p,
+                                                  _stream_ptr(seed.device)),
+          "vits_attention_dropout_mask")
+    return mask
+
 
 def neg_cent(z_p: torch.Tensor, m_p: torch.Tensor, logs_p: torch.Tensor) -> torch.Tensor:
     """MAS scores [B, t_t, t_s] of models.py:483-490 in one fp32 MFMA kernel

@@ -39,14 +39,16 @@ from __future__ import annotations
 
 import collections
 import contextlib
+import math
 import os
 import sys
 
 import torch
 import torch.nn.functional as F
 from torch import nn
+from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _lib, ops
 from ._lib import (EPI_GATE, EPI_STORE, TILE_32x256, TILE_64x128, TILE_64x256, TILE_128x128,
                    WDT_BF16, WDT_F16, WDT_F32, ConvWgradDesc, check)
 from . import engine
@@ -1012,6 +1014,93 @@ def conv1d_cat(modules, x: torch.Tensor):
     b = None if m0.bias is None else torch.cat([m.bias for m in modules], 0)
     y = conv1d_hip(x, w, b, m0.dilation[0], m0.padding[0], 1.0, wdt)
     return y.split([m.out_channels for m in modules], 1)
+
+
+# ---------------------------------------------------------------------------
+# Self-attention core (attentions.py:85-100) in training
+# ---------------------------------------------------------------------------
+
+
+class AttentionHip(torch.autograd.Function):
+    """dropout(softmax(q k^T / sqrt(D), masked -1e4), p_drop) v on channel-major
+    [B, H*D, T] q / k / v of one dtype (fp32, or the 16-bit autocast type) -
+    csrc/attention.hip: one forward launch that saves the log-sum-exp, two
+    backward launches (dq by query tile, dk / dv by key tile) that recompute
+    the probabilities from it; the T x T matrices never reach memory.  The
+    dropout seed is a device int64 drawn from torch's generator (no host
+    sync; a captured graph draws a new one on every replay), kept for the
+    backward, which regenerates the same keep mask."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, n_heads: int, lengths, p_drop: float):
+        seed = (torch.empty(1, dtype=torch.int64, device=q.device).random_()
+                if p_drop > 0.0 else None)
+        out, lse = ops.attention_train_forward(q, k, v, n_heads, lengths, p_drop, seed)
+        ctx.save_for_backward(q, k, v, out, lse, lengths, seed)
+        ctx.n_heads, ctx.p_drop = n_heads, p_drop
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        q, k, v, out, lse, lengths, seed = ctx.saved_tensors
+        dout = dout.to(q.dtype)
+        if dout.stride(2) != 1 or dout.stride(1) != dout.shape[2]:
+            dout = dout.contiguous()
+        dq, dk, dv = ops.attention_backward(q, k, v, out, dout, lse, ctx.n_heads, lengths,
+                                            ctx.p_drop, seed)
+        return dq, dk, dv, None, None, None
+
+
+def _attention_torch(q, k, v, n_heads: int, mask, p_drop: float, training: bool):
+    b, d, t_s = k.size()
+    t_t = q.size(2)
+    D = d // n_heads
+    qh = q.view(b, n_heads, D, t_t).transpose(2, 3)
+    kh = k.view(b, n_heads, D, t_s).transpose(2, 3)
+    vh = v.view(b, n_heads, D, t_s).transpose(2, 3)
+    scores = torch.matmul(qh / math.sqrt(D), kh.transpose(-2, -1))
+    if mask is not None:
+        scores = scores.masked_fill(mask == 0, -1e4)
+    p = F.dropout(F.softmax(scores, dim=-1), p_drop, training)
+    return torch.matmul(p, vh).transpose(2, 3).contiguous().view(b, d, t_t)
+
+
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n_heads: int, lengths,
+              p_drop: float, training: bool, mask: torch.Tensor | None = None) -> torch.Tensor:
+    """The attention core of MultiHeadAttention.forward on [B, H*D, T] q / k /
+    v.  The HIP op (AttentionHip) on a ROCm device with HIP_TRAIN and
+    attentions.ATTN_HIP on, a supported head dim, lengths given and equal
+    query / key lengths - in fp32 training (autocast off) on fp32 tensors,
+    inside a 16-bit autocast region on the tensors autocast casts for a
+    matmul (fp32 / fp16 / bf16, cast to the autocast dtype as it does).
+    ``lengths`` (int [B]) IS the mask there: ``mask`` is ignored and must be
+    the outer product of the length masks ([B, 1, T, T]) or None; a mask of
+    any other shape takes the torch path.
+    Otherwise (float64 tensors and 16-bit tensors outside autocast included,
+    which keep their dtype) the reference's matmul / masked_fill / softmax /
+    dropout / matmul chain on torch with ``mask``."""
+    from . import attentions
+
+    wdt = train_wdtype(q)
+    D = q.shape[1] // n_heads
+    B, _, T = q.shape
+    if (wdt is None or not attentions.ATTN_HIP or lengths is None
+            or D not in ops.ATTN_HEAD_DIMS or q.shape != k.shape or k.shape != v.shape
+            or (mask is not None and mask.shape != (B, 1, T, T))):
+        return _attention_torch(q, k, v, n_heads, mask, p_drop, training)
+    dt = torch.float32 if wdt == WDT_F32 else _TORCH_16[wdt]
+    # what autocast casts to dt (it leaves float64 alone); with autocast off
+    # only fp32 tensors, so that no module changes its arithmetic or dtype
+    castable = ((torch.float32,) if wdt == WDT_F32 else
+                (torch.float32, torch.float16, torch.bfloat16))
+    if any(t.dtype not in castable for t in (q, k, v)):
+        return _attention_torch(q, k, v, n_heads, mask, p_drop, training)
+    if not (q.dtype == k.dtype == v.dtype == dt and q.stride() == k.stride() == v.stride()
+            and q.stride(2) == 1 and q.stride(1) == T):
+        q, k, v = (t.to(dt).contiguous() for t in (q, k, v))
+    return AttentionHip.apply(q, k, v, n_heads, lengths.to(torch.int32),
+                              p_drop if training else 0.0)
 
 
 # ---------------------------------------------------------------------------
