@@ -38,6 +38,9 @@
  *                            (attentions.py:85-100)
  *   vits_attention_train_forward /  the same core in training, with its
  *   vits_attention_backward         dropout (attentions.py:97) and gradients
+ *   vits_resample_poly /     the output stage of VITSWrap.speaking
+ *   vits_pcm16               (vits_wrap.py:186-197): librosa.resample for
+ *                            pitch and sampling rate, clip, int16, tail pad
  */
 #ifndef VITS_AMD_H
 #define VITS_AMD_H
@@ -745,6 +748,41 @@ int vits_bias_lrelu_workspace(int64_t rows, int C);
 int vits_bias_lrelu_backward(const void* g, const void* out, void* dy, float* db,
                              float* workspace, int ws_floats, int64_t rows, int C, float slope,
                              int wdtype, void* stream);
+
+/* ---------------------------------------------------------------------- */
+/* PCM output stage of VITSWrap.speaking (vits_wrap.py:186-197): the pitch */
+/* / sampling-rate resampling and the int16 conversion, on the device.     */
+/* vits_resample_poly = scipy.signal.resample_poly(x, up, down) with its   */
+/* defaults (Kaiser 5.0, zero extension), per row of x [batch][x_cap]      */
+/* (`x_dtype` VITS_DT_F32 / _F16 / _BF16, row stride x_bstride elements):  */
+/*   out[n] = sum_i x[i] * h[n*down - i*up + half_len], n < n_out =        */
+/*   ceil(n_in * up / down), fp32 accumulation in a fixed order.           */
+/* up / down are used as given: reduce them by their gcd to get scipy's    */
+/* filter.  half_len = 10 * max(up, down); h has 2 * half_len + 1 taps     */
+/* (float32(firwin(...)) * float32(up)) and is passed by phase: `table`    */
+/* [table_rows = up][table_k = ceil((2 * half_len + 1) / up)] fp32,        */
+/* table[r][k] = h[r + k * up], 0 past the last tap.  up == down == 1 is a */
+/* copy (table ignored, may be NULL).                                      */
+/* Row length n_in: `lens` NULL -> n_host for every row (then n_host >     */
+/* x_cap or n_out > out_cap is VITS_E_SHAPE); else lens[b] * len_scale,    */
+/* int32 [batch] read on the device and clamped to [0, x_cap] (n_out to    */
+/* out_cap).  x at or past n_in counts as zero whatever the buffer holds.  */
+/* Exactly one output, [batch][out_cap] with row stride out_bstride:       */
+/* `out` fp32, or `pcm` int16 = clip(float32(float32(v * volume) * 32767), */
+/* -32768, 32767) truncated toward zero (the host expression, bit for      */
+/* bit).  Either is written as zero from n_out to out_cap.  `out_lens`     */
+/* (int32 [batch], NULL = skip) receives n_out, so that a second pass can  */
+/* take its lengths from the device.                                       */
+/* vits_pcm16: the int16 conversion alone (n_out = n_in).                  */
+/* ---------------------------------------------------------------------- */
+int vits_resample_poly(const void* x, int x_dtype, int64_t x_bstride, int x_cap,
+                       const int32_t* lens, int len_scale, int n_host, const float* table,
+                       int table_rows, int table_k, int up, int down, int half_len, float* out,
+                       int16_t* pcm, int64_t out_bstride, int out_cap, float volume,
+                       int32_t* out_lens, int batch, void* stream);
+int vits_pcm16(const void* x, int x_dtype, int64_t x_bstride, int x_cap, const int32_t* lens,
+               int len_scale, int n_host, float volume, int16_t* pcm, int64_t out_bstride,
+               int out_cap, int batch, void* stream);
 
 /* library introspection */
 const char* vits_amd_version(void);

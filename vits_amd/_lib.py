@@ -413,6 +413,17 @@ _SIGS = {
     "vits_bias_lrelu_backward": (
         C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_int, C.c_float, C.c_int,
                                      C.c_void_p]),
+    "vits_resample_poly": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p,
+                           C.c_int, C.c_void_p],
+    ),
+    "vits_pcm16": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
+         C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p],
+    ),
     "vits_amd_version": (C.c_char_p, []),
     "vits_amd_device_arch": (C.c_int, [C.c_char_p, C.c_int]),
     "vits_dispatch_count": (C.c_int64, [C.c_int]),

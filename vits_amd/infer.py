@@ -141,7 +141,8 @@ class EmoVITS(object):
         self._p1_graphs[t_x] = run  # most recently used last
         return tuple(t.clone() for t in run(text_t, emo, sid))
 
-    def infer(self, spkid, text, emo, *, duration_rate=1.0):
+    def _inputs(self, spkid, text, emo):
+        """Speaker mapping and emotion lookup of infer (infer.py:135-158)."""
         x_length = text.shape[0]
         spkid = self.spkid_mapping.get(spkid, spkid)
         assert spkid < self.num_speaker, f"spkid={spkid} must be less than {self.num_speaker}"
@@ -157,9 +158,18 @@ class EmoVITS(object):
             emo = self._get_spk_emo_embed(emo).unsqueeze(0)
         text_t = torch.from_numpy(np.ascontiguousarray(text)).half().to(self.device).unsqueeze(0)
         emo = emo.to(self.device)
+        return x_length, text_t, emo, sid
 
+    def infer(self, spkid, text, emo, *, duration_rate=1.0):
+        x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
         if self.graph and x_length <= 4096:
             return self._infer_graph(text_t, emo, sid, duration_rate), emo
+        wav = self._infer_eager(x_length, text_t, emo, sid, duration_rate)
+        return wav.float().view(-1).cpu().numpy(), emo
+
+    def _infer_eager(self, x_length, text_t, emo, sid, duration_rate):
+        """The reference's sequence: infer_p1 -> host durations -> infer_p2;
+        the waveform stays on the device."""
         m_p, s_p, logw, g = self._infer_p1(text_t, emo, sid)
         w = torch.exp(logw) * duration_rate
         w_ceil = torch.ceil(w)
@@ -168,19 +178,98 @@ class EmoVITS(object):
         start = np.random.randint(max(1, self.noise.size(0) - nl))
         noise = self.noise[start:start + nl].view(1, self.inter_channels, y_length)
         attn = infer_path(w_ceil.float(), x_length, y_length).half()
-        wav = self.model.infer_p2(attn, m_p, s_p, g, noise)
-        return wav.float().view(-1).cpu().numpy(), emo
+        return self.model.infer_p2(attn, m_p, s_p, g, noise)
+
+    def _post_passes(self, pitch, sampling_rate):
+        """The (up, down) resampling passes of VITSWrap.speaking, in its
+        order: pitch (int(sr / pitch) -> sr), then the rate change (sr ->
+        sampling_rate); a step that leaves the rate as it is is dropped."""
+        sr = self.sampling_rate
+        steps = []
+        if pitch != 1.0:
+            steps.append((int(sr / pitch), sr))
+        if sampling_rate != sr:
+            steps.append((sr, sampling_rate))
+        passes = [ops.resample_ratio(o, t) for o, t in steps if o != t]
+        return [(u, d) for u, d in passes if u != d]
+
+    def _post(self, wav, passes, volume, tail, *, lengths, length_scale=1):
+        """wav [1, cap] -> int16 [1, >= n_out + tail] on the current stream:
+        every pass but the last writes an fp32 intermediate and its length,
+        the last one (or pcm16 alone) the PCM, zero past its end."""
+        cap = wav.shape[1] if isinstance(lengths, torch.Tensor) else int(lengths)
+        x = wav
+        for i, (up, down) in enumerate(passes):
+            cap = ops.resample_out_len(cap, up, down)
+            if i == len(passes) - 1:
+                break
+            mid = torch.empty(1, max(1, cap), device=wav.device, dtype=torch.float32)
+            if isinstance(lengths, torch.Tensor):
+                nxt = torch.empty(1, device=wav.device, dtype=torch.int32)
+                ops.resample_poly(x, up, down, lengths=lengths, length_scale=length_scale,
+                                  out=mid, out_lengths=nxt)
+                lengths, length_scale = nxt, 1
+            else:
+                ops.resample_poly(x, up, down, lengths=lengths, out=mid)
+                lengths = cap
+            x = mid
+        pcm = torch.empty(1, max(1, cap + tail), device=wav.device, dtype=torch.int16)
+        if passes:
+            up, down = passes[-1]
+            return ops.resample_pcm16(x, up, down, volume, lengths=lengths,
+                                      length_scale=length_scale, out=pcm)
+        return ops.pcm16(x, volume, lengths=lengths, length_scale=length_scale, out=pcm)
+
+    def infer_pcm(self, spkid, text, emo, *, duration_rate=1.0, pitch=1.0, sampling_rate=None,
+                  volume=1.0, tail_silence=0.0):
+        """infer plus the output stage of VITSWrap.speaking (vits_wrap.py:
+        186-197) on the device: pitch / sampling-rate resampling
+        (ops.resample_poly), volume, clip and int16 conversion, tail silence.
+        Only the int16 PCM is copied to the host.  In graph mode the post
+        kernels are plain launches right behind the utterance graph, over the
+        whole bucket, with the length read from the graph's y_len on the
+        device; the one host sync stays the y_len read.  Draws from numpy's
+        generator exactly as infer does.  On a CPU device: infer and the host
+        chain.  Returns (pcm int16 [n], emo, n_model_samples)."""
+        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
+        tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
+        if self.device.type != "cuda":
+            from . import vits_wrap
+
+            wav, emo = self.infer(spkid, text, emo, duration_rate=duration_rate)
+            pcm = vits_wrap.host_pcm(wav, self.sampling_rate, pitch, sampling_rate, volume,
+                                     tail_silence)
+            return pcm, emo, len(wav)
+        passes = self._post_passes(pitch, sampling_rate)
+        x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
+        if self.graph and x_length <= 4096:
+            pcm, n = self._infer_graph(
+                text_t, emo, sid, duration_rate,
+                post=lambda wav, y_len: self._post(wav, passes, volume, tail, lengths=y_len,
+                                                   length_scale=self.hop_size))
+            n *= self.hop_size
+        else:
+            wav = self._infer_eager(x_length, text_t, emo, sid, duration_rate)
+            n = wav.shape[-1]
+            pcm = self._post(wav.reshape(1, -1), passes, volume, tail, lengths=n)
+        n_out = n
+        for up, down in passes:
+            n_out = ops.resample_out_len(n_out, up, down)
+        return pcm[0, :n_out + tail].cpu().numpy(), emo, n
 
 
     # text tokens are padded to a multiple of TX_BUCKET (masked encoder);
     # frame buckets are powers of two from 256 up to the noise buffer's 4096
     TX_BUCKET = 32
 
-    def _infer_graph(self, text_t, emo, sid, duration_rate):
+    def _infer_graph(self, text_t, emo, sid, duration_rate, post=None):
         """One replay of the whole-utterance graph; the one host sync is the
         waveform copy (y_len read with it).  A bucket that turns out too
         small (y_len > frames) is re-run once at a large enough bucket,
-        which this text bucket keeps from then on."""
+        which this text bucket keeps from then on.  ``post(wav [1, frames *
+        hop], y_len int32 [1])`` is launched behind every replay, before the
+        sync; its result is then returned with the frame count, in place of
+        the waveform."""
         t_x = text_t.shape[1]
         xb = -(-t_x // self.TX_BUCKET) * self.TX_BUCKET
         while True:
@@ -200,6 +289,7 @@ class EmoVITS(object):
             # reference, and the generator ends where the reference's does
             pool, state = ops.numpy_draw_pool()
             wav, y_len = run(text_t, emo, sid, noise_start=pool, x_length=t_x)
+            posted = None if post is None else post(wav[0], y_len[0])
             n, used = (int(v) for v in y_len[:, 0].tolist())  # (synchronises)
             if n <= tyb and used == -2:
                 # every word of the pool was rejected (p < 2^-32): numpy's
@@ -213,6 +303,8 @@ class EmoVITS(object):
                     raise ValueError(f"utterance of {n} frames does not fit the "
                                      f"{self.noise.numel()}-sample noise buffer")
                 ops.numpy_draw_commit(state, used)
+                if post is not None:
+                    return posted, n
                 return wav[0, 0, :n * self.hop_size].float().cpu().numpy()
             np.random.set_state(state)  # re-run at a larger bucket: same draw
             if tyb >= 4096:

@@ -9,8 +9,10 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import threading
 from dataclasses import dataclass, field
+from fractions import Fraction
 from typing import Optional
 
 import numpy as np
@@ -1289,3 +1291,146 @@ def stft_mag(x: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int, win: i
     # cast outside the Function so autograd returns the gradient in x's dtype
     # (fp16 under autocast, as y_hat is in train_stft.py)
     return _StftMag.apply(x.float(), window, n_fft, hop, win, pad, eps)
+
+
+# ---------------------------------------------------------------------------
+# PCM output stage: polyphase resampler + int16 epilogue (csrc/post.hip)
+# ---------------------------------------------------------------------------
+
+
+def resample_ratio(orig_sr: int, target_sr: int) -> tuple[int, int]:
+    """(up, down) of one resampling step of the wrappers (pitch, sampling
+    rate): target / orig as a fraction with a denominator of at most 1000."""
+    fr = Fraction(int(target_sr), int(orig_sr)).limit_denominator(1000)
+    return fr.numerator, fr.denominator
+
+
+def _reduced(up: int, down: int) -> tuple[int, int]:
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise _lib.VitsAmdError(f"resample: up and down must be >= 1, got {up}/{down}")
+    g = math.gcd(up, down)
+    return up // g, down // g
+
+
+def resample_out_len(n: int, up: int, down: int) -> int:
+    """len(scipy.signal.resample_poly(x[:n], up, down)) = ceil(n * up / down)."""
+    up, down = _reduced(up, down)
+    return -(-int(n) * up // down)
+
+
+_RESAMPLE_FILTERS: dict = {}
+
+
+def resample_filter(up: int, down: int, device="cpu") -> tuple[torch.Tensor, int]:
+    """(table, half_len) of resample_poly's default filter for up / down
+    (reduced by their gcd): h = float32(firwin(2 * half_len + 1, 1 / max(up,
+    down), window=('kaiser', 5.0))) * float32(up), half_len = 10 * max(up,
+    down), laid out by phase for the kernel: table [up, K] fp32 with
+    table[r, k] = h[r + k * up] (zero past the last tap), so that
+    table.t().reshape(-1)[:2 * half_len + 1] is h.  Designed once per (up,
+    down, device) and cached; up == down has no filter."""
+    up, down = _reduced(up, down)
+    if up == down:
+        raise _lib.VitsAmdError("resample_filter: up == down is a copy, it has no filter")
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (up, down, device)
+    hit = _RESAMPLE_FILTERS.get(key)
+    if hit is None:
+        from scipy.signal import firwin
+
+        half_len = 10 * max(up, down)
+        h = firwin(2 * half_len + 1, 1.0 / max(up, down), window=("kaiser", 5.0))
+        h = h.astype(np.float32) * np.float32(up)
+        k = -(-(2 * half_len + 1) // up)
+        flat = np.zeros(k * up, dtype=np.float32)
+        flat[:h.size] = h
+        table = torch.from_numpy(np.ascontiguousarray(flat.reshape(k, up).T)).to(device)
+        hit = _RESAMPLE_FILTERS[key] = (table, half_len)
+    return hit
+
+
+def _post_launch(what, x, up, down, lengths, length_scale, out, out_lengths, volume, pcm):
+    require_device(x, out, out_lengths)
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise _lib.VitsAmdError(f"{what}: x must be fp32, fp16 or bf16, got {x.dtype}")
+    if x.dim() not in (1, 2) or x.stride(-1) != 1 or x.shape[-1] < 1:
+        raise _lib.VitsAmdError(f"{what}: x must be [n] or [B, n] with unit stride along n")
+    rows = x if x.dim() == 2 else x.unsqueeze(0)
+    B, cap = rows.shape
+    up, down = _reduced(up, down)
+    if isinstance(lengths, torch.Tensor):
+        require_device(lengths)
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or not lengths.is_contiguous():
+            raise _lib.VitsAmdError(f"{what}: lengths must be a contiguous int32 [{B}] tensor")
+        lens_ptr, n_host, n_max = lengths.data_ptr(), 0, cap
+    else:
+        lens_ptr, n_host = None, cap if lengths is None else int(lengths)
+        n_max = n_host
+    odt = torch.int16 if pcm else torch.float32
+    if out is None:
+        out = torch.empty(B, max(1, resample_out_len(n_max, up, down)), device=x.device, dtype=odt)
+        out_rows = out
+    else:
+        out_rows = out if out.dim() == 2 else out.unsqueeze(0)
+        if (out.dtype != odt or out.dim() != x.dim() or out_rows.shape[0] != B
+                or out.stride(-1) != 1 or out.shape[-1] < 1):
+            raise _lib.VitsAmdError(f"{what}: out must be {odt}, {x.dim()}-d like x, unit stride")
+    if out_lengths is not None and (out_lengths.dtype != torch.int32
+                                    or tuple(out_lengths.shape) != (B,)
+                                    or not out_lengths.is_contiguous()):
+        raise _lib.VitsAmdError(f"{what}: out_lengths must be a contiguous int32 [{B}] tensor")
+    x_bstride = rows.stride(0) if B > 1 else cap
+    out_cap = out_rows.shape[1]
+    out_bstride = out_rows.stride(0) if B > 1 else out_cap
+    lib = _lib.load()
+    if up == down and pcm and out_lengths is None:
+        check(lib.vits_pcm16(rows.data_ptr(), _DT[x.dtype], x_bstride, cap, lens_ptr,
+                             int(length_scale), n_host, float(volume), out_rows.data_ptr(),
+                             out_bstride, out_cap, B, _stream_ptr(x.device)), what)
+    else:
+        table, half_len = (None, 0) if up == down else resample_filter(up, down, x.device)
+        check(lib.vits_resample_poly(
+            rows.data_ptr(), _DT[x.dtype], x_bstride, cap, lens_ptr, int(length_scale), n_host,
+            _ptr(table), up, 0 if table is None else table.shape[1], up, down, half_len,
+            None if pcm else out_rows.data_ptr(), out_rows.data_ptr() if pcm else None,
+            out_bstride, out_cap, float(volume), _ptr(out_lengths), B, _stream_ptr(x.device)),
+            what)
+    return out if x.dim() == 2 else out.reshape(-1)
+
+
+def resample_poly(x: torch.Tensor, up: int, down: int, *, lengths=None, length_scale: int = 1,
+                  out: Optional[torch.Tensor] = None,
+                  out_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scipy.signal.resample_poly(x, up, down) (defaults: Kaiser 5.0, zero
+    extension) along the last axis of x [n] or [B, n] (fp32 / fp16 / bf16),
+    fp32 out.  Row length: ``lengths`` None = all of x, an int = the same
+    host length for every row, or an int32 [B] device tensor times the host
+    integer ``length_scale`` (frame counts times the hop), read on the device
+    without a host sync.  Samples at or past the length count as zero and
+    out is zero from n_out = resample_out_len(length, up, down) to its end;
+    ``out_lengths`` (int32 [B]) receives n_out for a following pass.  With
+    ``out`` and ``out_lengths`` given, and the ratio's filter already cached
+    (resample_filter, one eager call), the call allocates nothing and can be
+    captured in a graph.  up == down (after reduction) is a masked copy."""
+    return _post_launch("resample_poly", x, up, down, lengths, length_scale, out, out_lengths,
+                        1.0, False)
+
+
+def resample_pcm16(x: torch.Tensor, up: int, down: int, volume: float = 1.0, *, lengths=None,
+                   length_scale: int = 1, out: Optional[torch.Tensor] = None,
+                   out_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """resample_poly with the int16 epilogue of pcm16 fused into the pass:
+    int16 out, zero (silence) past n_out."""
+    return _post_launch("resample_pcm16", x, up, down, lengths, length_scale, out, out_lengths,
+                        volume, True)
+
+
+def pcm16(x: torch.Tensor, volume: float = 1.0, *, lengths=None, length_scale: int = 1,
+          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """np.clip(x * volume * 32767, -32768, 32767).astype(np.int16) on the
+    device, bit for bit for fp32 x (two fp32 multiplies in that order,
+    truncation toward zero); zero past the row length (see resample_poly)."""
+    return _post_launch("pcm16", x, 1, 1, lengths, length_scale, out, None, volume, True)

@@ -13,11 +13,11 @@ from __future__ import annotations
 
 import struct
 import time
-from fractions import Fraction
 
 import numpy as np
 import torch
 
+from . import ops
 from .infer import EmoVITS
 
 
@@ -36,8 +36,21 @@ def _resample(wav, orig_sr, target_sr):
 
     if orig_sr == target_sr:
         return wav
-    fr = Fraction(int(target_sr), int(orig_sr)).limit_denominator(1000)
-    return resample_poly(wav, fr.numerator, fr.denominator).astype(np.float32)
+    up, down = ops.resample_ratio(orig_sr, target_sr)
+    return resample_poly(wav, up, down).astype(np.float32)
+
+
+def host_pcm(wav, model_sr, pitch, sampling_rate, volume, tail_silence):
+    """The host output stage of ``speaking`` (vits_wrap.py:186-197): pitch
+    and sampling-rate resampling, volume, clip, int16, tail silence."""
+    if pitch != 1.0:
+        wav = _resample(wav, int(model_sr / pitch), model_sr)
+    if sampling_rate != model_sr:
+        wav = _resample(wav, model_sr, sampling_rate)
+    wav = np.clip(wav * volume * 32767, -32768, 32767).astype(np.int16)
+    if tail_silence > 0:
+        wav = np.pad(wav, [0, int(tail_silence * sampling_rate)])
+    return wav
 
 
 class VITSWrap(object):
@@ -48,13 +61,17 @@ class VITSWrap(object):
     default_tail_silece = 0.0
 
     def __init__(self, ckpt_path: str = None, device: torch.device = None, loglv: int = 0, *,
-                 textparser=None, speecher: EmoVITS = None):
+                 textparser=None, speecher: EmoVITS = None, device_post: bool = False):
+        """device_post: run the output stage (resampling, volume, int16, tail
+        silence) on the GPU behind the synthesis (EmoVITS.infer_pcm) and copy
+        only the int16 PCM to the host; off: the host chain (scipy / numpy)."""
         if textparser is None:
             raise ValueError("VITSWrap needs a text front-end (the reference's private `textparser` "
                              "is not available): pass textparser=...")
         self.loglv = loglv
         self.textparser = textparser
         self.speecher = speecher if speecher is not None else EmoVITS(ckpt_path, device=device)
+        self.device_post = bool(device_post) and self.speecher.device.type == "cuda"
         self.asv = None  # optional bandwidth extension (fbandext) is not part of the reference tree
         self.default_sampling_rate = self.speecher.sampling_rate
         self.max_utt_length = getattr(self.textparser, "max_utt_length", 256)
@@ -109,15 +126,16 @@ class VITSWrap(object):
             uid, segtext, vec = self.textparser(uid, text)
             t1 = time.time()
             t_front += t1 - t0
-            wav, emotion = self.speecher.infer(spkid, vec, emotion, duration_rate=speed)
-            batch_wavlen += len(wav)
-            if pitch != 1.0:
-                wav = _resample(wav, int(self.default_sampling_rate / pitch), self.default_sampling_rate)
-            if sampling_rate != self.default_sampling_rate:
-                wav = _resample(wav, self.default_sampling_rate, sampling_rate)
-            wav = np.clip(wav * volume * 32767, -32768, 32767).astype(np.int16)
-            if tail_silence > 0:
-                wav = np.pad(wav, [0, int(tail_silence * sampling_rate)])
+            if self.device_post:
+                wav, emotion, n_model = self.speecher.infer_pcm(
+                    spkid, vec, emotion, duration_rate=speed, pitch=pitch,
+                    sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence)
+                batch_wavlen += n_model
+            else:
+                wav, emotion = self.speecher.infer(spkid, vec, emotion, duration_rate=speed)
+                batch_wavlen += len(wav)
+                wav = host_pcm(wav, self.default_sampling_rate, pitch, sampling_rate, volume,
+                               tail_silence)
             batch_wav.append(wav)
             t_back += time.time() - t1
             end_ms += len(wav) / sampling_rate * 1000
