@@ -41,6 +41,11 @@
  *   vits_resample_poly /     the output stage of VITSWrap.speaking
  *   vits_pcm16               (vits_wrap.py:186-197): librosa.resample for
  *                            pitch and sampling rate, clip, int16, tail pad
+ *   vits_draw_starts         the np.random.randint slice starts of
+ *                            consecutive EmoVITS.infer calls (infer.py:173),
+ *                            for a whole batch in call order
+ *   vits_pack_pcm            the segment concatenation of VITSWrap.speaking
+ *                            (vits_wrap.py:198,212-214), on the device
  */
 #ifndef VITS_AMD_H
 #define VITS_AMD_H
@@ -232,6 +237,30 @@ int vits_expand_durations(const float* logw, int64_t logw_bstride, const int32_t
                           float noise_scale, float* z,
                           int batch, int channels, int t_y, int32_t* lens,
                           const int32_t* stage_mult, int n_stage, void* stream);
+
+/* noise_mode 2: the slice start of row b is read from noise_start taken as  */
+/* the int64 [batch] `starts` of vits_draw_starts (8-byte aligned); a       */
+/* negative start, or one whose slice would leave the buffer, gives z = 0   */
+/* and reads no noise.  lens has n_stage rows, as in mode 0.                */
+
+/* ---------------------------------------------------------------------- */
+/* The noise-slice starts of a batch as consecutive EmoVITS.infer calls     */
+/* draw them (infer.py:173): one launch of one workgroup computes y_len[b]  */
+/* of every row with vits_expand_durations' arithmetic, then draws row b's  */
+/* np.random.randint(noise_len - channels * y_len[b]) from ONE shared pool  */
+/* of raw MT19937 words (uint32 [pool_n]), starting where row b - 1's       */
+/* masked rejection stopped.  starts int64 [batch]; meta int32 [2 * batch   */
+/* + 1] = y_len [batch] | status [batch] | used_total.  status: words       */
+/* consumed (0 when the range has one value: numpy draws nothing), -1 when  */
+/* the slice does not fit (nothing consumed), -2 when the pool ran out at   */
+/* this row; starts[b] = -1 for a negative status.  Rows at or past         */
+/* *n_rows (device int32, NULL = batch: the padding of a batch bucket) draw */
+/* nothing: status 0, start 0.  t_x <= 4096, batch <= 1024.                 */
+/* ---------------------------------------------------------------------- */
+int vits_draw_starts(const float* logw, int64_t logw_bstride, const int32_t* x_len, int t_x,
+                     float rate, int half_round, int channels, int64_t noise_len,
+                     const uint32_t* pool, int pool_n, const int32_t* n_rows, int batch,
+                     int64_t* starts, int32_t* meta, void* stream);
 
 int vits_conv_post_tanh(const float* x, int64_t x_bstride, int32_t x_cstride, const float* w,
                         float* y, int batch, int channels, int t_len, int ksize, void* stream);
@@ -783,6 +812,20 @@ int vits_resample_poly(const void* x, int x_dtype, int64_t x_bstride, int x_cap,
 int vits_pcm16(const void* x, int x_dtype, int64_t x_bstride, int x_cap, const int32_t* lens,
                int len_scale, int n_host, float volume, int16_t* pcm, int64_t out_bstride,
                int out_cap, int batch, void* stream);
+
+/* Ragged pack behind the last pass (a request's segments in one copy):    */
+/* rows int16 [batch][cap] (row stride bstride) -> out int16 [out_cap]:     */
+/* row b's first n_out[b] samples at out + offsets[b], then `tail` zeros;   */
+/* n_out[b] = y_len[b] * hop passed through ceil(n * up[i] / down[i]) for   */
+/* each of the n_passes <= 2 (reduced) ratios, offsets[b + 1] = offsets[b]  */
+/* + n_out[b] + tail.  y_len int32 [batch] and *n_rows (NULL = batch) are   */
+/* read on the device; rows at or past *n_rows add nothing.  offsets int32  */
+/* [batch + 1].  Nothing is written at or past out_cap; samples past a      */
+/* row's cap read as zero.  batch <= 64.                                    */
+int vits_pack_pcm(const int16_t* rows, int64_t bstride, int cap, const int32_t* y_len, int hop,
+                  const int32_t* up, const int32_t* down, int n_passes, int tail,
+                  const int32_t* n_rows, int batch, int32_t* offsets, int16_t* out,
+                  int64_t out_cap, void* stream);
 
 /* library introspection */
 const char* vits_amd_version(void);

@@ -11,7 +11,9 @@
 //   vits_expand_durations durations -> lengths + expanded prior on the device
 //                         (models.py:544-553, commons.py:143-155), the
 //                         host sync of infer() removed
-//   vits_conv_post_tanh   Generator tail, models.py:315-317
+//   vits_draw_starts      the noise-slice starts of a batch (infer.py:173's
+//                         randint of consecutive calls) in one launch
+//   vits_conv_post_tanh  Generator tail, models.py:315-317
 #include "common.h"
 
 namespace {
@@ -148,20 +150,20 @@ struct EdStages {
   int n;
 };
 
-__global__ __launch_bounds__(256) void expand_durations_kernel(
-    const float* __restrict__ logw, int64_t logw_bstride, const int32_t* __restrict__ x_len,
-    int t_x, float rate, int half_round, const float* __restrict__ m, const float* __restrict__ s,
-    int64_t ms_bstride, int ms_cstride, const float* __restrict__ noise, int noise_mode,
-    const int32_t* __restrict__ noise_start, int64_t noise_len, float noise_scale,
-    float* __restrict__ z, int channels, int t_y, int batch, int32_t* __restrict__ lens,
-    const EdStages st) {
-  __shared__ int cum[ED_MAX_TX];
-  __shared__ int part[256];
-  __shared__ int xi[ED_T];
-  const int b = blockIdx.y;
+// The integer durations of one utterance and their inclusive scan, by a whole
+// 256-thread workgroup: cum[x] = sum_{x' <= x} ceil(exp(logw[x']) * rate) for
+// x < t_x (tokens at or past nx last 0 frames), `total` = cum[t_x - 1];
+// returns y_len = max(total, 1) (the half model's fp16 sum applied).  The
+// one place this arithmetic lives: expand_durations_kernel expands with it
+// and draw_starts_kernel sizes the noise slices with it, so the two cannot
+// disagree about a length.  Every thread of the workgroup must call it; cum
+// and part are valid for all threads on return (callers that reuse them
+// synchronise first).
+__device__ __forceinline__ int ed_scan_durations(const float* __restrict__ logw_row, int nx,
+                                                 int t_x, float rate, int half_round, int* cum,
+                                                 int* part, int& total) {
   const int tid = threadIdx.x;
-  const int nx = x_len ? min(x_len[b], t_x) : t_x;
-  // 1) integer durations of this thread's consecutive tokens, block scan
+  // integer durations of this thread's consecutive tokens, block scan
   const int per = (t_x + 255) / 256;
   const int xb0 = tid * per;
   int local = 0;
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(256) void expand_durations_kernel(
     if (x < t_x) {
       int d = 0;
       if (x < nx) {
-        float w = expf(logw[(int64_t)b * logw_bstride + x]);
+        float w = expf(logw_row[x]);
         if (half_round) w = (float)(_Float16)w;  // the fp16 model's torch.exp
         w = w * rate;
         if (half_round) w = (float)(_Float16)w;
@@ -198,8 +200,47 @@ __global__ __launch_bounds__(256) void expand_durations_kernel(
   // torch.sum result rounds to half: totals > 2048 frames round to even)
   int y_len = part[255];
   if (half_round) y_len = (int)(float)(_Float16)(float)y_len;
-  y_len = max(y_len, 1);
-  const int total = part[255];
+  total = part[255];
+  return max(y_len, 1);
+}
+
+// numpy's legacy RandomState.randint(high) for high - 1 = rng in [1, 2^32):
+// the first raw MT19937 word u of pool[pos, n) with (u & mask) <= rng, mask =
+// the smallest 2^k - 1 >= rng (masked rejection).  Returns the number of
+// words consumed (the accepted one included) and the value in `val`, or -2
+// when every remaining word was rejected.
+__device__ __forceinline__ int ed_masked_draw(const uint32_t* __restrict__ pool, int pos, int n,
+                                              uint32_t rng, uint32_t& val) {
+  uint32_t mask = rng;
+  mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4;
+  mask |= mask >> 8; mask |= mask >> 16;
+  for (int i = pos; i < n; ++i) {
+    const uint32_t u = pool[i] & mask;
+    if (u <= rng) {
+      val = u;
+      return i + 1 - pos;
+    }
+  }
+  return -2;
+}
+
+__global__ __launch_bounds__(256) void expand_durations_kernel(
+    const float* __restrict__ logw, int64_t logw_bstride, const int32_t* __restrict__ x_len,
+    int t_x, float rate, int half_round, const float* __restrict__ m, const float* __restrict__ s,
+    int64_t ms_bstride, int ms_cstride, const float* __restrict__ noise, int noise_mode,
+    const int32_t* __restrict__ noise_start, int64_t noise_len, float noise_scale,
+    float* __restrict__ z, int channels, int t_y, int batch, int32_t* __restrict__ lens,
+    const EdStages st) {
+  __shared__ int cum[ED_MAX_TX];
+  __shared__ int part[256];
+  __shared__ int xi[ED_T];
+  const int b = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int nx = x_len ? min(x_len[b], t_x) : t_x;
+  // 1) integer durations, their scan and y_len
+  int total;
+  const int y_len = ed_scan_durations(logw + (int64_t)b * logw_bstride, nx, t_x, rate, half_round,
+                                      cum, part, total);
   if (blockIdx.x == 0 && tid < st.n) lens[tid * batch + b] = y_len * st.mult[tid];
   // 2) token of each frame of this workgroup: first x with cum[x] > t
   const int t0 = blockIdx.x * ED_T;
@@ -233,7 +274,14 @@ __global__ __launch_bounds__(256) void expand_durations_kernel(
   // noise element is read.
   int64_t nbase = 0;
   bool noise_ok = true;
-  if (noise_mode) {
+  // mode 2: the start was drawn beforehand, in batch order from one shared
+  // pool (draw_starts_kernel below): noise_start is its int64 [B] output, a
+  // negative start = no slice for this row (z = 0, no noise element read);
+  // a start whose slice would leave the buffer counts as negative too.
+  if (noise_mode == 2) {
+    nbase = reinterpret_cast<const int64_t*>(noise_start)[b];
+    noise_ok = nbase >= 0 && nbase + (int64_t)channels * y_len <= noise_len;
+  } else if (noise_mode) {
     const int64_t high = noise_len - (int64_t)channels * y_len;
     int used = -1;
     if (high >= 1 && high - 1 <= 0xFFFFFFFFll) {
@@ -241,20 +289,10 @@ __global__ __launch_bounds__(256) void expand_durations_kernel(
       if (rng == 0) {
         used = 0;
       } else {
-        used = -2;  // (until a word is accepted)
-        uint32_t mask = rng;
-        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4;
-        mask |= mask >> 8; mask |= mask >> 16;
-        const uint32_t* pool = reinterpret_cast<const uint32_t*>(noise_start) +
-                               (int64_t)b * ED_DRAWS;
-        for (int i = 0; i < ED_DRAWS; ++i) {
-          const uint32_t u = pool[i] & mask;
-          if (u <= rng) {
-            nbase = u;
-            used = i + 1;
-            break;
-          }
-        }
+        uint32_t u = 0;
+        used = ed_masked_draw(reinterpret_cast<const uint32_t*>(noise_start) +
+                                  (int64_t)b * ED_DRAWS, 0, ED_DRAWS, rng, u);
+        nbase = u;
       }
     }
     noise_ok = used >= 0;
@@ -276,6 +314,58 @@ __global__ __launch_bounds__(256) void expand_durations_kernel(
     }
     z[((int64_t)b * channels + c) * t_y + t] = v;
   }
+}
+
+// ---------------------------------------------------------------------------
+// Noise-slice starts of a whole batch, drawn in row order from ONE pool of
+// raw MT19937 words: row b's np.random.randint(noise_len - C * y_len[b])
+// (infer.py:173) starts in the word stream where row b - 1's rejection
+// sampling stopped, as consecutive EmoVITS.infer calls leave numpy's
+// generator.  One workgroup: the rows' y_len come one after another from
+// ed_scan_durations (the arithmetic of expand_durations_kernel), thread 0
+// carries the pool position from row to row.  status[b] = words consumed
+// (0 when rng == 0: numpy draws nothing), -1 when the slice does not fit
+// (nothing consumed), -2 when the pool ran out at this row (later rows that
+// need a word get -2 as well); starts[b] = -1 for a negative status.  Rows at
+// or past *n_rows (the padding of a batch bucket) draw nothing: status 0,
+// start 0.  meta = [y_len (batch) | status (batch) | used_total].
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void draw_starts_kernel(
+    const float* __restrict__ logw, int64_t logw_bstride, const int32_t* __restrict__ x_len,
+    int t_x, float rate, int half_round, int channels, int64_t noise_len,
+    const uint32_t* __restrict__ pool, int pool_n, const int32_t* __restrict__ n_rows_p,
+    int batch, int64_t* __restrict__ starts, int32_t* __restrict__ meta) {
+  __shared__ int cum[ED_MAX_TX];
+  __shared__ int part[256];
+  const int n_rows = n_rows_p ? min(max(*n_rows_p, 0), batch) : batch;
+  int pos = 0;  // (thread 0's) next unread word of the pool
+  for (int b = 0; b < batch; ++b) {
+    const int nx = x_len ? min(x_len[b], t_x) : t_x;
+    int total;
+    const int y_len = ed_scan_durations(logw + (int64_t)b * logw_bstride, nx, t_x, rate,
+                                        half_round, cum, part, total);
+    __syncthreads();  // cum / part are rewritten for the next row
+    if (threadIdx.x == 0) {
+      int64_t start = 0;
+      int used = 0;
+      if (b < n_rows) {
+        const int64_t high = noise_len - (int64_t)channels * y_len;
+        if (high < 1 || high - 1 > 0xFFFFFFFFll) {
+          used = -1;
+        } else if (high > 1) {
+          uint32_t u = 0;
+          used = ed_masked_draw(pool, pos, pool_n, (uint32_t)(high - 1), u);
+          start = u;
+          pos = used > 0 ? pos + used : pool_n;
+        }
+        if (used < 0) start = -1;
+      }
+      starts[b] = start;
+      meta[b] = y_len;
+      meta[batch + b] = used;
+    }
+  }
+  if (threadIdx.x == 0) meta[2 * batch] = pos;
 }
 
 // ---------------------------------------------------------------------------
@@ -441,7 +531,9 @@ extern "C" int vits_expand_durations(const float* logw, int64_t logw_bstride,
                  t_x > 0);
   VITS_CHECK_ARG(n_stage >= 1 && n_stage <= ED_MAX_STAGES && (n_stage == 1 || stage_mult));
   VITS_CHECK_SHAPE(t_x <= ED_MAX_TX && ms_cstride >= t_x);
-  VITS_CHECK_ARG(noise_mode == 0 || (noise_mode == 1 && noise_start));
+  VITS_CHECK_ARG(noise_mode == 0 || ((noise_mode == 1 || noise_mode == 2) && noise_start));
+  if (noise_mode == 2)  // int64 [batch] starts of vits_draw_starts
+    VITS_CHECK_ARG((reinterpret_cast<uintptr_t>(noise_start) & 7) == 0 && noise_len > 0);
   EdStages st;
   st.n = n_stage;
   for (int i = 0; i < ED_MAX_STAGES; ++i) st.mult[i] = i < n_stage ? (stage_mult ? stage_mult[i] : 1) : 0;
@@ -450,6 +542,21 @@ extern "C" int vits_expand_durations(const float* logw, int64_t logw_bstride,
                      logw_bstride, x_len, t_x, rate, half_round, m, s, ms_bstride, ms_cstride,
                      noise, noise_mode, noise_start, noise_len, noise_scale, z, channels, t_y,
                      batch, lens, st);
+  return vits_launch_status();
+}
+
+extern "C" int vits_draw_starts(const float* logw, int64_t logw_bstride, const int32_t* x_len,
+                                int t_x, float rate, int half_round, int channels,
+                                int64_t noise_len, const uint32_t* pool, int pool_n,
+                                const int32_t* n_rows, int batch, int64_t* starts, int32_t* meta,
+                                void* stream) {
+  VITS_CHECK_ARG(logw && pool && starts && meta && batch > 0 && channels > 0 && t_x > 0 &&
+                 pool_n > 0 && noise_len > 0);
+  VITS_CHECK_ARG((reinterpret_cast<uintptr_t>(starts) & 7) == 0);
+  VITS_CHECK_SHAPE(t_x <= ED_MAX_TX && batch <= 1024 && logw_bstride >= t_x);
+  hipLaunchKernelGGL(draw_starts_kernel, dim3(1), dim3(256), 0, as_stream(stream), logw,
+                     logw_bstride, x_len, t_x, rate, half_round, channels, noise_len, pool, pool_n,
+                     n_rows, batch, starts, meta);
   return vits_launch_status();
 }
 

@@ -128,7 +128,84 @@ int post_dispatch(const void* x, int x_dtype, int64_t x_bstride, int x_cap, cons
   }
 }
 
+// ---------------------------------------------------------------------------
+// Ragged pack behind the last pass: the rows of a batch, each cut at its own
+// length and followed by `tail` zeros, back to back in one int16 stream, with
+// the int32 row offsets beside it (one device-to-host copy returns a whole
+// request).  n_out[b] = y_len[b] * hop through ceil(n * up / down) per pass
+// (ops.resample_out_len on reduced ratios); offset[b + 1] = offset[b] +
+// n_out[b] + tail for b < *n_rows, offset[b + 1] = offset[b] for the padding
+// rows of a batch bucket.  Workgroup = (2048 samples of row b, b): every
+// workgroup recomputes the prefix over the rows before its own (batch <= 64
+// integer steps, no atomics, no second launch).  Samples past the row's
+// buffer (a y_len beyond the bucket: the caller re-runs) read as zero and
+// nothing is written at or past stream_cap.
+// ---------------------------------------------------------------------------
+constexpr int PK_MAX_PASSES = 2;
+constexpr int PK_MAX_BATCH = 64;
+constexpr int PK_T = 2048;
+struct PackPasses {
+  int32_t up[PK_MAX_PASSES];
+  int32_t down[PK_MAX_PASSES];
+  int n;
+};
+
+__device__ __forceinline__ int64_t pack_row_len(int32_t frames, int hop, const PackPasses& pp) {
+  int64_t n = (int64_t)max(frames, 0) * hop;
+  for (int i = 0; i < pp.n; ++i) n = (n * pp.up[i] + pp.down[i] - 1) / pp.down[i];
+  return n;
+}
+
+__global__ __launch_bounds__(256) void pack_pcm_kernel(
+    const int16_t* __restrict__ rows, int64_t bstride, int cap, const int32_t* __restrict__ y_len,
+    int hop, const PackPasses pp, int tail, const int32_t* __restrict__ n_rows_p, int batch,
+    int32_t* __restrict__ offsets, int16_t* __restrict__ stream, int64_t stream_cap) {
+  const int b = blockIdx.y;
+  const int n_rows = n_rows_p ? min(max(*n_rows_p, 0), batch) : batch;
+  if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
+    int64_t off = 0;
+    offsets[0] = 0;
+    for (int r = 0; r < batch; ++r) {
+      if (r < n_rows) off += pack_row_len(y_len[r], hop, pp) + tail;
+      offsets[r + 1] = (int32_t)min(off, (int64_t)INT32_MAX);
+    }
+  }
+  if (b >= n_rows) return;
+  int64_t off = 0;
+  for (int r = 0; r < b; ++r) off += pack_row_len(y_len[r], hop, pp) + tail;
+  const int64_t n_out = pack_row_len(y_len[b], hop, pp);
+  const int16_t* src = rows + (int64_t)b * bstride;
+  for (int k = 0; k < PK_T / 256; ++k) {
+    const int64_t i = (int64_t)blockIdx.x * PK_T + k * 256 + threadIdx.x;
+    if (i >= n_out + tail || off + i >= stream_cap) break;
+    stream[off + i] = (i < n_out && i < cap) ? src[i] : (int16_t)0;
+  }
+}
+
 }  // namespace
+
+extern "C" int vits_pack_pcm(const int16_t* rows, int64_t bstride, int cap, const int32_t* y_len,
+                             int hop, const int32_t* up, const int32_t* down, int n_passes,
+                             int tail, const int32_t* n_rows, int batch, int32_t* offsets,
+                             int16_t* out, int64_t out_cap, void* stream) {
+  VITS_CHECK_ARG(rows && y_len && offsets && out && batch > 0 && cap > 0 && hop >= 1 &&
+                 tail >= 0 && out_cap > 0);
+  VITS_CHECK_ARG(n_passes >= 0 && n_passes <= PK_MAX_PASSES && (n_passes == 0 || (up && down)));
+  VITS_CHECK_SHAPE(batch <= PK_MAX_BATCH && bstride >= cap);
+  PackPasses pp;
+  pp.n = n_passes;
+  for (int i = 0; i < PK_MAX_PASSES; ++i) {
+    pp.up[i] = i < n_passes ? up[i] : 1;
+    pp.down[i] = i < n_passes ? down[i] : 1;
+    VITS_CHECK_ARG(pp.up[i] >= 1 && pp.down[i] >= 1);
+  }
+  const int64_t n_max = (int64_t)cap + tail;  // the longest row a buffer row can hold
+  VITS_CHECK_SHAPE(n_max <= INT32_MAX);
+  const dim3 grid((unsigned)((n_max + PK_T - 1) / PK_T), batch);
+  hipLaunchKernelGGL(pack_pcm_kernel, grid, dim3(256), 0, as_stream(stream), rows, bstride, cap,
+                     y_len, hop, pp, tail, n_rows, batch, offsets, out, out_cap);
+  return vits_launch_status();
+}
 
 extern "C" int vits_resample_poly(const void* x, int x_dtype, int64_t x_bstride, int x_cap,
                                   const int32_t* lens, int len_scale, int n_host,

@@ -28,8 +28,9 @@ class EmoVITS(object):
         (SynthesizerTrn.capture_infer_bucketed: the durations, the output
         length and the path computed on the device, no host sync before the
         waveform copy), graphs cached per (text bucket, frame bucket), at
-        most ``max_graphs``; graph=False: the reference's eager sequence
-        (infer_p1 -> host durations -> infer_p2)."""
+        most ``max_graphs`` (the batched graphs of infer_batch /
+        infer_pcm_batch included); graph=False: the reference's eager
+        sequence (infer_p1 -> host durations -> infer_p2)."""
         self.loglv = loglv
         self.graph_cache = int(graph_cache)
         self._p1_graphs = {}
@@ -37,6 +38,7 @@ class EmoVITS(object):
         self.max_graphs = int(max_graphs)
         self._graphs = {}
         self._ty_bucket = {}
+        self._pinned = {}
         if checkpoint_path is None and model is None:
             checkpoint_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "checkpoint",
                                            "checkpoint.pth")
@@ -141,12 +143,12 @@ class EmoVITS(object):
         self._p1_graphs[t_x] = run  # most recently used last
         return tuple(t.clone() for t in run(text_t, emo, sid))
 
-    def _inputs(self, spkid, text, emo):
-        """Speaker mapping and emotion lookup of infer (infer.py:135-158)."""
-        x_length = text.shape[0]
+    def _resolve(self, spkid, emo):
+        """Speaker mapping and emotion lookup of infer (infer.py:135-158):
+        (mapped spkid, emo fp16 [1, 1024] on the device).  A lookup without
+        an emotion id draws it from numpy's generator."""
         spkid = self.spkid_mapping.get(spkid, spkid)
         assert spkid < self.num_speaker, f"spkid={spkid} must be less than {self.num_speaker}"
-        sid = torch.tensor([spkid], dtype=torch.long, device=self.device)
         if isinstance(emo, torch.Tensor):
             emo = emo.half()
         else:
@@ -156,16 +158,24 @@ class EmoVITS(object):
                 emo = tuple([self.spkid_mapping.get(emo[0], emo[0]) if emo[0] != 0 else spkid,
                              -1 if len(emo) == 1 else emo[1]])
             emo = self._get_spk_emo_embed(emo).unsqueeze(0)
+        return spkid, emo.to(self.device)
+
+    def _inputs(self, spkid, text, emo):
+        x_length = text.shape[0]
+        spkid, emo = self._resolve(spkid, emo)
+        sid = torch.tensor([spkid], dtype=torch.long, device=self.device)
         text_t = torch.from_numpy(np.ascontiguousarray(text)).half().to(self.device).unsqueeze(0)
-        emo = emo.to(self.device)
         return x_length, text_t, emo, sid
 
     def infer(self, spkid, text, emo, *, duration_rate=1.0):
         x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
+        return self._infer_one(x_length, text_t, emo, sid, duration_rate), emo
+
+    def _infer_one(self, x_length, text_t, emo, sid, duration_rate):
         if self.graph and x_length <= 4096:
-            return self._infer_graph(text_t, emo, sid, duration_rate), emo
+            return self._infer_graph(text_t, emo, sid, duration_rate)
         wav = self._infer_eager(x_length, text_t, emo, sid, duration_rate)
-        return wav.float().view(-1).cpu().numpy(), emo
+        return wav.float().view(-1).cpu().numpy()
 
     def _infer_eager(self, x_length, text_t, emo, sid, duration_rate):
         """The reference's sequence: infer_p1 -> host durations -> infer_p2;
@@ -194,18 +204,19 @@ class EmoVITS(object):
         return [(u, d) for u, d in passes if u != d]
 
     def _post(self, wav, passes, volume, tail, *, lengths, length_scale=1):
-        """wav [1, cap] -> int16 [1, >= n_out + tail] on the current stream:
+        """wav [B, cap] -> int16 [B, >= n_out + tail] on the current stream:
         every pass but the last writes an fp32 intermediate and its length,
         the last one (or pcm16 alone) the PCM, zero past its end."""
+        B = wav.shape[0]
         cap = wav.shape[1] if isinstance(lengths, torch.Tensor) else int(lengths)
         x = wav
         for i, (up, down) in enumerate(passes):
             cap = ops.resample_out_len(cap, up, down)
             if i == len(passes) - 1:
                 break
-            mid = torch.empty(1, max(1, cap), device=wav.device, dtype=torch.float32)
+            mid = torch.empty(B, max(1, cap), device=wav.device, dtype=torch.float32)
             if isinstance(lengths, torch.Tensor):
-                nxt = torch.empty(1, device=wav.device, dtype=torch.int32)
+                nxt = torch.empty(B, device=wav.device, dtype=torch.int32)
                 ops.resample_poly(x, up, down, lengths=lengths, length_scale=length_scale,
                                   out=mid, out_lengths=nxt)
                 lengths, length_scale = nxt, 1
@@ -213,7 +224,7 @@ class EmoVITS(object):
                 ops.resample_poly(x, up, down, lengths=lengths, out=mid)
                 lengths = cap
             x = mid
-        pcm = torch.empty(1, max(1, cap + tail), device=wav.device, dtype=torch.int16)
+        pcm = torch.empty(B, max(1, cap + tail), device=wav.device, dtype=torch.int16)
         if passes:
             up, down = passes[-1]
             return ops.resample_pcm16(x, up, down, volume, lengths=lengths,
@@ -232,16 +243,22 @@ class EmoVITS(object):
         generator exactly as infer does.  On a CPU device: infer and the host
         chain.  Returns (pcm int16 [n], emo, n_model_samples)."""
         sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
+        x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
+        pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, duration_rate, pitch,
+                                     sampling_rate, volume, tail_silence)
+        return pcm, emo, n
+
+    def _infer_pcm_one(self, x_length, text_t, emo, sid, duration_rate, pitch, sampling_rate,
+                       volume, tail_silence):
         tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
         if self.device.type != "cuda":
             from . import vits_wrap
 
-            wav, emo = self.infer(spkid, text, emo, duration_rate=duration_rate)
+            wav = self._infer_one(x_length, text_t, emo, sid, duration_rate)
             pcm = vits_wrap.host_pcm(wav, self.sampling_rate, pitch, sampling_rate, volume,
                                      tail_silence)
-            return pcm, emo, len(wav)
+            return pcm, len(wav)
         passes = self._post_passes(pitch, sampling_rate)
-        x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
         if self.graph and x_length <= 4096:
             pcm, n = self._infer_graph(
                 text_t, emo, sid, duration_rate,
@@ -255,7 +272,205 @@ class EmoVITS(object):
         n_out = n
         for up, down in passes:
             n_out = ops.resample_out_len(n_out, up, down)
-        return pcm[0, :n_out + tail].cpu().numpy(), emo, n
+        return pcm[0, :n_out + tail].cpu().numpy(), n
+
+    # -- batched serving: all segments of a request in one utterance graph --------
+    MAX_BATCH = 16
+    BATCH_BUCKETS = (2, 4, 8, 16)
+
+    @classmethod
+    def _batch_bucket(cls, n):
+        """The smallest batch bucket that holds n rows."""
+        for b in cls.BATCH_BUCKETS:
+            if n <= b:
+                return b
+        raise ValueError(f"{n} rows exceed the largest batch bucket {cls.BATCH_BUCKETS[-1]}")
+
+    @classmethod
+    def _groups(cls, n):
+        """[(lo, hi)] consecutive groups of at most MAX_BATCH items, in order."""
+        step = max(1, min(int(cls.MAX_BATCH), cls.BATCH_BUCKETS[-1]))
+        return [(lo, min(lo + step, n)) for lo in range(0, n, step)]
+
+    def _resolve_items(self, items):
+        """All emotion lookups (their numpy draws) first, in item order; the
+        noise draws follow in item order.  That is the order of a
+        VITSWrap.speaking request, whose first segment looks the emotion up
+        and whose later segments reuse the returned tensor."""
+        items = list(items)
+        resolved = [self._resolve(spkid, emo) for spkid, _, emo in items]
+        texts = [np.ascontiguousarray(text) for _, text, _ in items]
+        return texts, [s for s, _ in resolved], [e for _, e in resolved]
+
+    def _batchable(self, texts):
+        return self.graph and self.device.type == "cuda" and max(t.shape[0] for t in texts) <= 4096
+
+    def _one_tensors(self, spkid, text):
+        sid = torch.tensor([spkid], dtype=torch.long, device=self.device)
+        return text.shape[0], torch.from_numpy(text).half().to(self.device).unsqueeze(0), sid
+
+    def infer_batch(self, items, *, duration_rate=1.0):
+        """infer for items = [(spkid, text [N, c], emo), ...]: [(wav float32
+        [n], emo), ...], bit for bit what a loop over infer returns for emo
+        tensors (see _resolve_items for the order of numpy draws otherwise),
+        with numpy's generator left where the loop leaves it.  Groups of up
+        to MAX_BATCH items run as ONE replay of a batched utterance graph
+        (batch buckets 2, 4, 8, 16); a single item, a CPU device or
+        graph=False run infer's path per item."""
+        texts, spkids, emos = self._resolve_items(items)
+        if not texts:
+            return []
+        out = []
+        for lo, hi in self._groups(len(texts)):
+            if hi - lo == 1 or not self._batchable(texts[lo:hi]):
+                for i in range(lo, hi):
+                    x_length, text_t, sid = self._one_tensors(spkids[i], texts[i])
+                    out.append((self._infer_one(x_length, text_t, emos[i], sid, duration_rate),
+                                emos[i]))
+                continue
+            wav, y = self._infer_graph_batch(texts[lo:hi], emos[lo:hi], spkids[lo:hi],
+                                             duration_rate)
+            hop = self.hop_size
+            host = wav[:hi - lo, 0, :max(y) * hop].cpu()  # one copy for the group
+            out += [(host[i, :n * hop].float().numpy(), emos[lo + i]) for i, n in enumerate(y)]
+        return out
+
+    def infer_pcm_batch(self, items, *, duration_rate=1.0, pitch=1.0, sampling_rate=None,
+                        volume=1.0, tail_silence=0.0):
+        """infer_pcm for items = [(spkid, text, emo), ...] that share one
+        rate, pitch, sampling rate, volume and tail: (pcm int16 [total],
+        offsets int64 [len + 1], emos, n_model list).  Item i's PCM, its tail
+        silence included, is pcm[offsets[i]:offsets[i + 1]], sample for
+        sample what infer_pcm returns; numpy's generator ends where the loop
+        over infer_pcm leaves it.  A group of up to MAX_BATCH items is one
+        graph replay, the post passes over all its rows, the ragged pack
+        (ops.pack_pcm) and ONE device-to-host copy with the one host sync:
+        offsets, lengths and draw status arrive in front of the samples."""
+        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
+        tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
+        texts, spkids, emos = self._resolve_items(items)
+        chunks, offsets, n_model = [], [0], []
+        for lo, hi in self._groups(len(texts)):
+            if hi - lo == 1 or not self._batchable(texts[lo:hi]):
+                for i in range(lo, hi):
+                    x_length, text_t, sid = self._one_tensors(spkids[i], texts[i])
+                    pcm, n = self._infer_pcm_one(x_length, text_t, emos[i], sid, duration_rate,
+                                                 pitch, sampling_rate, volume, tail_silence)
+                    chunks.append(pcm)
+                    offsets.append(offsets[-1] + len(pcm))
+                    n_model.append(n)
+                continue
+            passes = self._post_passes(pitch, sampling_rate)
+            (pcm, offs), y = self._infer_graph_batch(
+                texts[lo:hi], emos[lo:hi], spkids[lo:hi], duration_rate,
+                post=lambda wav, y_len, n_rows, words: self._post_pack(
+                    wav, y_len, n_rows, words, passes, volume, tail))
+            chunks.append(pcm)
+            offsets += [offsets[-1] + int(o) for o in offs[1:]]
+            n_model += [n * self.hop_size for n in y]
+        pcm = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int16)
+        return pcm, np.asarray(offsets, dtype=np.int64), emos, n_model
+
+    def _post_pack(self, wav, y_len, n_rows, words, passes, volume, tail):
+        """The post passes over every row of the bucket, then the ragged
+        pack: one int16 buffer, in front of the samples the int32 words
+        [offsets (B + 1) | words (y_len, status, used_total: 2 B + 1)]."""
+        B = wav.shape[0]
+        rows = self._post(wav, passes, volume, tail, lengths=y_len, length_scale=self.hop_size)
+        header = -(-2 * (3 * B + 2) // 8) * 8
+        out, _, _ = ops.pack_pcm(rows, y_len, self.hop_size, passes, tail, n_rows=n_rows,
+                                 header=header)
+        torch.cat(words, out=out[2 * (B + 1):2 * (3 * B + 2)].view(torch.int32))
+        return out
+
+    def _to_host(self, t):
+        """One device-to-host copy of t through a reused pinned buffer, and
+        the host sync that completes it."""
+        n = t.numel()
+        buf = self._pinned.get(t.dtype)
+        if buf is None or buf.numel() < n:
+            buf = self._pinned[t.dtype] = torch.empty(max(n, 1 << 16), dtype=t.dtype,
+                                                      pin_memory=True)
+        buf[:n].copy_(t.reshape(-1), non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return buf[:n].numpy().copy()
+
+    def _infer_graph_batch(self, texts, emos, spkids, duration_rate, post=None):
+        """2..16 utterances as one replay of a batched utterance graph, cached
+        with the B = 1 graphs per (batch bucket, text bucket, frame bucket,
+        rate).  The noise starts are drawn on the device in row order from
+        ONE pool of raw words of numpy's generator (ops.draw_starts), so they
+        and the generator's final state are those of consecutive infer calls.
+        Returns (wav [B, 1, frames * hop] on the device, y_len list), or with
+        ``post(wav [B, frames * hop], y_len, n_rows, (y_len, status,
+        used_total))`` -> the int16 buffer of _post_pack: ((pcm, offsets),
+        y_len list) on the host after its single copy.  A row longer than the
+        frame bucket re-runs the group at a larger bucket (same draws), an
+        exhausted pool re-runs it with a pool twice as long."""
+        n = len(texts)
+        bb = self._batch_bucket(n)
+        lengths = [t.shape[0] for t in texts]
+        xb = -(-max(lengths) // self.TX_BUCKET) * self.TX_BUCKET
+        x = np.zeros((n, max(lengths), texts[0].shape[1]), dtype=np.float32)
+        for i, t in enumerate(texts):
+            x[i, :lengths[i]] = t
+        x = torch.from_numpy(x).half().to(self.device)
+        emo = torch.cat(emos)
+        sid = torch.tensor(spkids, dtype=torch.long)
+        pool_mult = 1
+        while True:
+            tyb = self._ty_bucket.get((bb, xb, duration_rate), 256)
+            key = (bb, xb, tyb, float(duration_rate))
+            run = self._graphs.pop(key, None)
+            if run is None:
+                while len(self._graphs) >= self.max_graphs:
+                    self._graphs.pop(next(iter(self._graphs)))
+                run = self.model.capture_infer_bucketed(
+                    xb, tyb, noise_len=self.noise.numel(), padded_text=True,
+                    length_scale=duration_rate, batch=bb)
+                run.static["noise"].copy_(self.noise.float())
+            self._graphs[key] = run  # most recently used last
+            pool, state = ops.numpy_draw_pool(run.pool_len * pool_mult)
+            if pool_mult == 1:
+                wav, y_len, status, used = run(x, emo, sid, lengths, pool, n)
+            else:
+                # the graph's pool is static: the (p < 2^-32 per row) longer
+                # pool runs the same kernels eagerly on the graph's inputs
+                st = run.static
+                wav, y_len, status, used = self.model.infer_bucketed(
+                    st["x"], st["emo"], st["sid"], st["noise"], tyb, x_lengths=st["xl"],
+                    length_scale=duration_rate, noise_start=torch.from_numpy(pool).to(self.device),
+                    n_rows=st["n_rows"])
+            words = (y_len, status, used)
+            if post is None:
+                host = torch.cat(words).tolist()  # (synchronises)
+            else:
+                packed = post(wav[:, 0], y_len, run.static["n_rows"], words)
+                header = -(-2 * (3 * bb + 2) // 8) * 8
+                row_cap = (packed.numel() - header) // bb  # (the padding rows hold nothing)
+                buf = self._to_host(packed[:header + n * row_cap])
+                host = buf[2 * (bb + 1):2 * (3 * bb + 2)].view(np.int32).tolist()
+            y, st_rows, used = host[:n], host[bb:bb + n], host[2 * bb]
+            if max(y) > tyb:
+                np.random.set_state(state)  # re-run at a larger bucket: same draws
+                if tyb >= 4096:
+                    raise RuntimeError(f"utterance of {max(y)} frames exceeds the 4096-frame "
+                                       "noise buffer")
+                self._ty_bucket[(bb, xb, duration_rate)] = min(4096, 1 << (max(y) - 1).bit_length())
+                continue
+            if -2 in st_rows:
+                np.random.set_state(state)
+                pool_mult *= 2
+                continue
+            if -1 in st_rows:
+                np.random.set_state(state)
+                raise ValueError(f"utterance of {y[st_rows.index(-1)]} frames does not fit the "
+                                 f"{self.noise.numel()}-sample noise buffer")
+            ops.numpy_draw_commit(state, used)
+            if post is None:
+                return wav, y
+            offs = buf[:2 * (bb + 1)].view(np.int32)[:n + 1]
+            return (buf[header:header + int(offs[n])], offs), y
 
 
     # text tokens are padded to a multiple of TX_BUCKET (masked encoder);

@@ -491,7 +491,7 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def infer_bucketed(self, x, emo, sid, noise, t_y, *, x_lengths=None, length_scale=1.0,
-                       noise_start=None):
+                       noise_start=None, n_rows=None):
         """infer (models.py:537-556) / EmoVITS.infer (infer.py:160-182) with
         NO host synchronisation, over a static bucket of t_y frames - the
         whole utterance can be captured into one hipGraph
@@ -514,9 +514,20 @@ class SynthesizerTrn(nn.Module):
         as TextEncoder.infer of each unpadded utterance (every layer masked,
         engine.TextEncoderPlan pad_exact); None: the exact-length infer_p1
         path (B = 1).  Returns (wav [B, 1, t_y * hop], y_len int32 [B]);
-        samples past y_len * hop are not meaningful (crop on the host)."""
+        samples past y_len * hop are not meaningful (crop on the host).
+
+        Shared-pool form (a batch that must draw as B consecutive EmoVITS
+        calls would): ``noise_start`` = int32 [P] raw words and ``n_rows``
+        (int or int32 [1] device tensor: rows at or past it are the padding
+        of a batch bucket and draw nothing).  ops.draw_starts draws every
+        row's start in row order from the one pool, the expansion reads them
+        (vits_expand_durations mode 2).  Returns (wav, y_len [B], status
+        [B], used_total [1]) as ops.draw_starts defines them."""
         engine._check_gpu(x, "SynthesizerTrn.infer_bucketed")
         dt = x.dtype
+        shared_pool = noise_start is not None and noise_start.dim() == 1
+        if shared_pool and n_rows is None:
+            n_rows = x.shape[0]
         if x_lengths is None:
             m_p, s_p, logw, g = self.infer_p1(x, emo, sid)
             xl = None
@@ -527,21 +538,29 @@ class SynthesizerTrn(nn.Module):
                                                         pad_exact=True)
             logw = engine.get_plan(self.dp, engine.DurationPlan).run(h, g, lengths=xl)
             m_p, s_p, logw = m_p.to(dt), s_p.to(dt), logw.to(dt)
+        starts = None
+        if shared_pool:
+            starts, y_len, status, used_total = engine.ops.draw_starts(
+                logw, m_p.shape[1], noise.numel(), noise_start, rate=float(length_scale),
+                x_len=xl, half_round=dt == torch.float16, n_rows=n_rows)
+            noise_start = None
         z, lens = engine.ops.expand_durations(
             logw, m_p, s_p, noise, int(t_y), rate=float(length_scale), x_len=xl,
             noise_start=noise_start, half_round=dt == torch.float16,
-            stage_mult=self._stage_mult())
+            stage_mult=self._stage_mult(), starts=starts)
         gf = engine._f32(g)
         with engine.ops.length_skip(64):
             engine.get_plan(self.flow, engine.CouplingFlowPlan).run_(z, gf, lengths=lens[0])
             o = engine.get_plan(self.dec, engine.GeneratorPlan).run(z, gf, lengths=lens[1:])
+        if shared_pool:
+            return o.to(m_p.dtype), y_len, status, used_total
         if noise_start is not None:
             return o.to(m_p.dtype), lens[0::len(lens) - 1]
         return o.to(m_p.dtype), lens[0]
 
     @torch.no_grad()
     def capture_infer_bucketed(self, t_x, t_y, *, noise_len=None, padded_text=False,
-                               length_scale=1.0, warmup=2):
+                               length_scale=1.0, warmup=2, batch=1, pool_len=None):
         """One hipGraph for a whole utterance (infer_bucketed) of t_x tokens
         (padded_text: up to t_x, x_lengths given at replay) into a t_y-frame
         bucket.  noise_len: replay reads a flat noise buffer of that many
@@ -549,7 +568,19 @@ class SynthesizerTrn(nn.Module):
         t_y].  Returns run(x, emo, sid, noise, noise_start=None,
         x_length=None) -> (wav, y_len) views of static buffers; with
         noise_len, noise_start is the [ops.ED_DRAWS] raw-word pool of
-        ops.numpy_draw_pool and y_len is [2, 1] (y_len, words consumed)."""
+        ops.numpy_draw_pool and y_len is [2, 1] (y_len, words consumed).
+
+        batch > 1 (needs padded_text and noise_len): one graph for up to
+        ``batch`` utterances, infer_bucketed's shared-pool form over a pool of
+        ``pool_len`` words (default ops.ED_DRAWS * batch).  Returns run(x [n,
+        t <= t_x, c], emo [n, 1024], sid [n], x_lengths (n ints), pool int32
+        [pool_len], n_rows=n) -> (wav [batch, 1, t_y * hop], y_len [batch],
+        status [batch], used_total [1]), views of static buffers.  Text rows
+        are zeroed past their length; rows at or past n are padding: zero
+        text, length 0 (y_len 1), no draw."""
+        if batch > 1:
+            return self._capture_infer_batch(t_x, t_y, int(batch), noise_len, padded_text,
+                                             length_scale, warmup, pool_len)
         dev = next(self.parameters()).device
         dt = next(self.parameters()).dtype
         C = self.inter_channels
@@ -597,6 +628,67 @@ class SynthesizerTrn(nn.Module):
         run.graph = graph
         run.static = static
         run.t_y = t_y
+        return run
+
+    def _capture_infer_batch(self, t_x, t_y, batch, noise_len, padded_text, length_scale, warmup,
+                             pool_len):
+        """capture_infer_bucketed for batch > 1 (see there)."""
+        if not padded_text or not noise_len:
+            raise ValueError("capture_infer_bucketed: batch > 1 needs padded_text=True and noise_len")
+        dev = next(self.parameters()).device
+        dt = next(self.parameters()).dtype
+        P = int(pool_len) if pool_len else engine.ops.ED_DRAWS * batch
+        static = dict(x=torch.zeros(batch, t_x, self.text_channels, device=dev, dtype=dt),
+                      emo=torch.zeros(batch, 1024, device=dev, dtype=dt),
+                      sid=torch.zeros(batch, device=dev, dtype=torch.long),
+                      xl=torch.zeros(batch, device=dev, dtype=torch.int32),
+                      pool=torch.zeros(P, device=dev, dtype=torch.int32),
+                      n_rows=torch.zeros(1, device=dev, dtype=torch.int32),
+                      noise=torch.zeros(noise_len, device=dev))
+        cols = torch.arange(t_x, device=dev).view(1, t_x, 1)
+
+        def body():
+            return self.infer_bucketed(static["x"], static["emo"], static["sid"], static["noise"],
+                                       t_y, x_lengths=static["xl"], length_scale=length_scale,
+                                       noise_start=static["pool"], n_rows=static["n_rows"])
+
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                body()
+        torch.cuda.current_stream(dev).wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = body()
+
+        def run(x, emo, sid, x_lengths, pool, n_rows=None):
+            n = x.shape[0] if n_rows is None else int(n_rows)
+            lengths = [int(v) for v in x_lengths][:n]
+            if not 1 <= n <= batch or len(lengths) != n or x.shape[1] > t_x or max(lengths) > x.shape[1]:
+                raise ValueError(f"batched replay: {n} rows of lengths {lengths} in x "
+                                 f"{tuple(x.shape)} do not fit [{batch}, {t_x}]")
+            static["xl"].copy_(torch.tensor(lengths + [0] * (batch - n), dtype=torch.int32))
+            static["x"].zero_()
+            static["x"][:n, :x.shape[1]].copy_(x[:n])
+            static["x"].masked_fill_(cols >= static["xl"].view(batch, 1, 1), 0)
+            static["emo"].zero_()
+            static["emo"][:n].copy_(emo[:n])
+            static["sid"].zero_()
+            static["sid"][:n].copy_(torch.as_tensor(sid)[:n])
+            pool = torch.as_tensor(pool, dtype=torch.int32).view(-1)
+            if pool.numel() != P:
+                raise ValueError(f"batched replay: the pool must have {P} words, got {pool.numel()}")
+            static["pool"].copy_(pool)
+            static["n_rows"].fill_(n)
+            graph.replay()
+            return out
+
+        run.graph = graph
+        run.static = static
+        run.t_y = t_y
+        run.batch = batch
+        run.pool_len = P
         return run
 
     # ------------------------------------------------------------ hipGraphs

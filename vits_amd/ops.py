@@ -916,7 +916,8 @@ def expand_durations(logw: torch.Tensor, m_p: torch.Tensor, s_p: torch.Tensor,
                      noise_scale: float = 1.0, x_len: Optional[torch.Tensor] = None,
                      noise_start: Optional[torch.Tensor] = None, half_round: bool = False,
                      stage_mult=(1,), out: Optional[torch.Tensor] = None,
-                     lens: Optional[torch.Tensor] = None):
+                     lens: Optional[torch.Tensor] = None,
+                     starts: Optional[torch.Tensor] = None):
     """Durations -> (z [B, C, t_y], lens int32 [n_stage, B]) on the device,
     without the host sync of models.py:547 / infer.py:171: w_ceil =
     ceil(exp(logw) * rate), y_len = max(sum, 1), z = the one-hot expansion of
@@ -929,8 +930,17 @@ def expand_durations(logw: torch.Tensor, m_p: torch.Tensor, s_p: torch.Tensor,
     legacy RandomState would, and ``lens`` gets one more row: the words
     consumed per utterance (-1: the slice does not fit; -2: every word of the
     pool was rejected, the caller advances by the pool and calls again; z is
-    zero for both)."""
+    zero for both).  ``starts`` (int64 [B], from ``draw_starts``) instead of
+    ``noise_start``: the flat buffer read at those explicit starts (a
+    negative one: z = 0, nothing read); ``lens`` stays [n_stage, B]."""
     require_device(logw, m_p, s_p, noise)
+    if starts is not None:
+        if noise_start is not None:
+            raise _lib.VitsAmdError("expand_durations: give noise_start or starts, not both")
+        require_device(starts)
+        if (tuple(starts.shape) != (m_p.shape[0],) or starts.dtype != torch.int64
+                or not starts.is_contiguous()):
+            raise _lib.VitsAmdError(f"expand_durations: starts must be int64 [{m_p.shape[0]}]")
     B, C_, t_x = m_p.shape
     logw = logw.reshape(B, t_x).float().contiguous()
     m_p = m_p.float().contiguous()
@@ -945,19 +955,81 @@ def expand_durations(logw: torch.Tensor, m_p: torch.Tensor, s_p: torch.Tensor,
     if tuple(lens.shape) != (rows, B) or lens.dtype != torch.int32 or not lens.is_contiguous():
         raise _lib.VitsAmdError(f"expand_durations: lens must be int32 [{rows}, {B}]")
     mult = (C.c_int32 * n_stage)(*[int(v) for v in stage_mult])
-    if noise_start is None:
+    if starts is not None:
+        mode, start_ptr = 2, starts.data_ptr()
+    elif noise_start is None:
         assert tuple(noise.shape) == (B, C_, t_y), noise.shape
+        mode, start_ptr = 0, None
     elif (tuple(noise_start.shape) != (B, ED_DRAWS) or noise_start.dtype != torch.int32
           or not noise_start.is_contiguous()):
         raise _lib.VitsAmdError(f"expand_durations: noise_start must be int32 [{B}, {ED_DRAWS}]")
+    else:
+        mode, start_ptr = 1, noise_start.data_ptr()
     check(_lib.load().vits_expand_durations(
         logw.data_ptr(), logw.stride(0), _ptr(x_len), t_x, float(rate), int(half_round),
         m_p.data_ptr(), s_p.data_ptr(), m_p.stride(0), m_p.stride(1), noise.data_ptr(),
-        0 if noise_start is None else 1, _ptr(noise_start), noise.numel(), float(noise_scale),
+        mode, start_ptr, noise.numel(), float(noise_scale),
         out.data_ptr(),
         B, C_, t_y, lens.data_ptr(), mult, n_stage, _stream_ptr(m_p.device)),
         "vits_expand_durations")
     return out, lens
+
+
+def _n_rows_ptr(n_rows, B: int, device, what: str):
+    """n_rows of the batched serving kernels: None (all B rows), a host int
+    or an int32 [1] device tensor (a graph's static buffer).  Returns the
+    tensor to keep alive and its pointer."""
+    if n_rows is None:
+        return None, None
+    if not isinstance(n_rows, torch.Tensor):
+        if not 0 <= int(n_rows) <= B:
+            raise _lib.VitsAmdError(f"{what}: n_rows must be in [0, {B}], got {n_rows}")
+        n_rows = torch.tensor([int(n_rows)], dtype=torch.int32, device=device)
+    require_device(n_rows)
+    if n_rows.dtype != torch.int32 or n_rows.numel() != 1:
+        raise _lib.VitsAmdError(f"{what}: n_rows must be an int or an int32 [1] device tensor")
+    return n_rows, n_rows.data_ptr()
+
+
+def draw_starts(logw: torch.Tensor, channels: int, noise_len: int, pool: torch.Tensor, *,
+                rate: float = 1.0, x_len: Optional[torch.Tensor] = None,
+                half_round: bool = False, n_rows=None, starts: Optional[torch.Tensor] = None,
+                meta: Optional[torch.Tensor] = None):
+    """The noise-slice starts of B utterances as B consecutive EmoVITS.infer
+    calls would draw them (infer.py:173): y_len[b] from ``logw`` with
+    expand_durations' arithmetic, then np.random.randint(noise_len - channels
+    * y_len[b]) in row order from ONE ``pool`` of raw MT19937 words (int32
+    [P] device tensor of ``numpy_draw_pool(P)``), row b reading on from where
+    row b - 1 stopped.  Returns (starts int64 [B], y_len int32 [B], status
+    int32 [B], used_total int32 [1]); the last three are views of ``meta``
+    (int32 [2 B + 1]).  status: words consumed, -1 = the slice does not fit
+    (nothing consumed), -2 = the pool ran out at this row; starts is -1 for
+    both.  Rows at or past ``n_rows`` (None, int or int32 [1] device tensor)
+    draw nothing.  When everything is >= 0, ``numpy_draw_commit(state,
+    used_total)`` leaves numpy's generator where the B calls would."""
+    require_device(logw, pool)
+    B = logw.shape[0]
+    logw = logw.reshape(B, -1).float().contiguous()
+    t_x = logw.shape[1]
+    if pool.dtype != torch.int32 or pool.dim() != 1 or not pool.is_contiguous() or not pool.numel():
+        raise _lib.VitsAmdError("draw_starts: pool must be a contiguous int32 [P] tensor, P >= 1")
+    if starts is None:
+        starts = torch.empty(B, device=logw.device, dtype=torch.int64)
+    if meta is None:
+        meta = torch.empty(2 * B + 1, device=logw.device, dtype=torch.int32)
+    if (tuple(starts.shape) != (B,) or starts.dtype != torch.int64 or not starts.is_contiguous()
+            or tuple(meta.shape) != (2 * B + 1,) or meta.dtype != torch.int32
+            or not meta.is_contiguous()):
+        raise _lib.VitsAmdError(f"draw_starts: starts must be int64 [{B}], meta int32 [{2 * B + 1}]")
+    if x_len is not None and (x_len.dtype != torch.int32 or tuple(x_len.shape) != (B,)
+                              or not x_len.is_contiguous()):
+        raise _lib.VitsAmdError(f"draw_starts: x_len must be a contiguous int32 [{B}] tensor")
+    keep, nr_ptr = _n_rows_ptr(n_rows, B, logw.device, "draw_starts")
+    check(_lib.load().vits_draw_starts(
+        logw.data_ptr(), logw.stride(0), _ptr(x_len), t_x, float(rate), int(half_round),
+        int(channels), int(noise_len), pool.data_ptr(), pool.numel(), nr_ptr, B,
+        starts.data_ptr(), meta.data_ptr(), _stream_ptr(logw.device)), "vits_draw_starts")
+    return starts, meta[:B], meta[B:2 * B], meta[2 * B:]
 
 
 def conv_post_tanh(x: torch.Tensor, weight: torch.Tensor, out: Optional[torch.Tensor] = None):
@@ -1434,3 +1506,57 @@ def pcm16(x: torch.Tensor, volume: float = 1.0, *, lengths=None, length_scale: i
     device, bit for bit for fp32 x (two fp32 multiplies in that order,
     truncation toward zero); zero past the row length (see resample_poly)."""
     return _post_launch("pcm16", x, 1, 1, lengths, length_scale, out, None, volume, True)
+
+
+PACK_MAX_BATCH = 64  # post.hip PK_MAX_BATCH
+
+
+def pack_header_len(B: int) -> int:
+    """int16 elements in front of pack_pcm's stream: the int32 [B + 1]
+    offsets, rounded up to 16 bytes."""
+    return -(-2 * (B + 1) // 8) * 8
+
+
+def pack_pcm(rows: torch.Tensor, y_len: torch.Tensor, hop: int, passes=(), tail: int = 0, *,
+             n_rows=None, out: Optional[torch.Tensor] = None, header: Optional[int] = None):
+    """A request's segments in one buffer: rows int16 [B, cap] (the last post
+    pass's output), each cut at n_out[b] = y_len[b] * hop passed through
+    resample_out_len for every (up, down) of ``passes`` (at most two) and
+    followed by ``tail`` zeros, written back to back.  ``out`` is ONE int16
+    tensor: int32 offsets [B + 1] in front (``header`` int16 elements, at
+    least pack_header_len(B); the caller may keep more words behind the
+    offsets), then the stream, so a single device-to-host copy returns both;
+    offsets[b + 1] = offsets[b] + n_out[b] + tail, rows at or past ``n_rows``
+    (None, int or int32 [1] device tensor) add nothing.  y_len (int32 [B])
+    and n_rows are read on the device: no host sync, capturable.  Returns
+    (out, offsets int32 [B + 1] view, stream int16 view)."""
+    require_device(rows, y_len, out)
+    if rows.dtype != torch.int16 or rows.dim() != 2 or rows.stride(1) != 1:
+        raise _lib.VitsAmdError("pack_pcm: rows must be int16 [B, cap] with unit stride along cap")
+    B, cap = rows.shape
+    if B > PACK_MAX_BATCH:
+        raise _lib.VitsAmdError(f"pack_pcm: at most {PACK_MAX_BATCH} rows, got {B}")
+    if y_len.dtype != torch.int32 or tuple(y_len.shape) != (B,) or not y_len.is_contiguous():
+        raise _lib.VitsAmdError(f"pack_pcm: y_len must be a contiguous int32 [{B}] tensor")
+    passes = [_reduced(u, d) for u, d in passes]
+    passes = [(u, d) for u, d in passes if u != d]
+    if len(passes) > 2:
+        raise _lib.VitsAmdError("pack_pcm: at most two resampling passes")
+    tail = int(tail)
+    header = pack_header_len(B) if header is None else int(header)
+    if header < pack_header_len(B) or header % 8:
+        raise _lib.VitsAmdError(f"pack_pcm: header must be a multiple of 8, >= {pack_header_len(B)}")
+    if out is None:
+        out = torch.empty(header + B * (cap + tail), device=rows.device, dtype=torch.int16)
+    if out.dtype != torch.int16 or out.dim() != 1 or not out.is_contiguous() or out.numel() <= header:
+        raise _lib.VitsAmdError("pack_pcm: out must be a contiguous int16 [> header] tensor")
+    offsets = out[:2 * (B + 1)].view(torch.int32)
+    stream = out[header:]
+    up = (C.c_int32 * 2)(*([u for u, _ in passes] + [1] * (2 - len(passes))))
+    down = (C.c_int32 * 2)(*([d for _, d in passes] + [1] * (2 - len(passes))))
+    keep, nr_ptr = _n_rows_ptr(n_rows, B, rows.device, "pack_pcm")
+    check(_lib.load().vits_pack_pcm(
+        rows.data_ptr(), rows.stride(0) if B > 1 else cap, cap, y_len.data_ptr(), int(hop), up,
+        down, len(passes), tail, nr_ptr, B, offsets.data_ptr(), stream.data_ptr(),
+        stream.numel(), _stream_ptr(rows.device)), "vits_pack_pcm")
+    return out, offsets, stream

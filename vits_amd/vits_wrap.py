@@ -60,18 +60,29 @@ class VITSWrap(object):
     default_pitch = 1.0
     default_tail_silece = 0.0
 
+    # batch_segments batches a request of at least this many segments; fewer
+    # run one after another (measured crossover: profiles/serve_batch_ab.txt)
+    BATCH_MIN_SEGMENTS = 2
+
     def __init__(self, ckpt_path: str = None, device: torch.device = None, loglv: int = 0, *,
-                 textparser=None, speecher: EmoVITS = None, device_post: bool = False):
+                 textparser=None, speecher: EmoVITS = None, device_post: bool = False,
+                 batch_segments: bool = False):
         """device_post: run the output stage (resampling, volume, int16, tail
         silence) on the GPU behind the synthesis (EmoVITS.infer_pcm) and copy
-        only the int16 PCM to the host; off: the host chain (scipy / numpy)."""
+        only the int16 PCM to the host; off: the host chain (scipy / numpy).
+        batch_segments (CUDA only; implies device_post): the front end runs
+        over all segments of a request first, then ONE
+        EmoVITS.infer_pcm_batch call synthesises them (one graph replay per
+        16 segments, one device-to-host copy); same result, same dict."""
         if textparser is None:
             raise ValueError("VITSWrap needs a text front-end (the reference's private `textparser` "
                              "is not available): pass textparser=...")
         self.loglv = loglv
         self.textparser = textparser
         self.speecher = speecher if speecher is not None else EmoVITS(ckpt_path, device=device)
-        self.device_post = bool(device_post) and self.speecher.device.type == "cuda"
+        self.batch_segments = bool(batch_segments) and self.speecher.device.type == "cuda"
+        self.device_post = ((bool(device_post) or self.batch_segments)
+                            and self.speecher.device.type == "cuda")
         self.asv = None  # optional bandwidth extension (fbandext) is not part of the reference tree
         self.default_sampling_rate = self.speecher.sampling_rate
         self.max_utt_length = getattr(self.textparser, "max_utt_length", 256)
@@ -119,26 +130,47 @@ class VITSWrap(object):
             self._parse_input(inputs)
         ids, texts = self._split_utt_text(utt_id, utt_text)
         batch_wav, batch_wavlen = [], 0
-        segment_info, start_ms, end_ms = [], 0.0, 0.0
+        segtexts, seg_samples = [], []  # per segment: front-end text, PCM samples (tail included)
         t_front, t_back = 0.0, 0.0
-        for uid, text in zip(ids, texts):
+        if self.batch_segments and len(texts) >= self.BATCH_MIN_SEGMENTS:
             t0 = time.time()
-            uid, segtext, vec = self.textparser(uid, text)
+            parsed = [self.textparser(uid, text) for uid, text in zip(ids, texts)]
             t1 = time.time()
-            t_front += t1 - t0
-            if self.device_post:
-                wav, emotion, n_model = self.speecher.infer_pcm(
-                    spkid, vec, emotion, duration_rate=speed, pitch=pitch,
-                    sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence)
-                batch_wavlen += n_model
-            else:
-                wav, emotion = self.speecher.infer(spkid, vec, emotion, duration_rate=speed)
-                batch_wavlen += len(wav)
-                wav = host_pcm(wav, self.default_sampling_rate, pitch, sampling_rate, volume,
-                               tail_silence)
-            batch_wav.append(wav)
-            t_back += time.time() - t1
-            end_ms += len(wav) / sampling_rate * 1000
+            t_front = t1 - t0
+            # the first segment looks the emotion up (its draw comes before
+            # every noise draw, as in the loop below); the others reuse it
+            _, emotion = self.speecher._resolve(spkid, emotion)
+            pcm, offsets, _, n_model = self.speecher.infer_pcm_batch(
+                [(spkid, vec, emotion) for _, _, vec in parsed], duration_rate=speed, pitch=pitch,
+                sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence)
+            batch_wav.append(pcm)
+            batch_wavlen = sum(n_model)
+            segtexts = [segtext for _, segtext, _ in parsed]
+            seg_samples = [int(n) for n in np.diff(offsets)]
+            t_back = time.time() - t1
+        else:
+            for uid, text in zip(ids, texts):
+                t0 = time.time()
+                uid, segtext, vec = self.textparser(uid, text)
+                t1 = time.time()
+                t_front += t1 - t0
+                if self.device_post:
+                    wav, emotion, n_model = self.speecher.infer_pcm(
+                        spkid, vec, emotion, duration_rate=speed, pitch=pitch,
+                        sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence)
+                    batch_wavlen += n_model
+                else:
+                    wav, emotion = self.speecher.infer(spkid, vec, emotion, duration_rate=speed)
+                    batch_wavlen += len(wav)
+                    wav = host_pcm(wav, self.default_sampling_rate, pitch, sampling_rate, volume,
+                                   tail_silence)
+                batch_wav.append(wav)
+                segtexts.append(segtext)
+                seg_samples.append(len(wav))
+                t_back += time.time() - t1
+        segment_info, start_ms, end_ms = [], 0.0, 0.0
+        for text, segtext, n in zip(texts, segtexts, seg_samples):
+            end_ms += n / sampling_rate * 1000
             segment_info.append({"start_ms": start_ms, "end_ms": end_ms, "input_text": text,
                                  "segtext": segtext.printer() if hasattr(segtext, "printer") else str(segtext)})
             start_ms = end_ms
