@@ -312,7 +312,9 @@ int vits_neg_cent(const float* z_p, const float* m_p, const float* logs_p, float
 /* torch.stft(center=True, pad_mode='reflect'); mel_processing pads       */
 /* (n_fft-hop)/2 itself and calls center=False), then framed with `hop`,  */
 /* windowed by `window` (length win, centred in n_fft as torch.stft does) */
-/* and transformed: frames = (L + 2 pad - n_fft)/hop + 1.                 */
+/* and transformed: frames = (L + 2 pad - n_fft)/hop + 1, and none when   */
+/* L + 2 pad < n_fft: the transforms then return VITS_E_SHAPE and         */
+/* vits_stft_workspace returns 0.                                         */
 /* mag [B][n_fft/2+1][frames] = sqrt(re^2 + im^2 + eps); re/im (optional, */
 /* needed by the backward) same layout.                                   */
 /* ---------------------------------------------------------------------- */

@@ -719,8 +719,10 @@ int make_job(StftJobD& J, const float* x, int batch, int length, const float* wi
   VITS_CHECK_ARG(window && batch > 0 && length > 0 && hop > 0 && win > 0);
   const int log2n = ilog2(n_fft);
   VITS_CHECK_SHAPE(log2n >= 1 && n_fft <= FFT_MAX && win <= n_fft && pad >= 0 && pad < length);
+  // a padded signal shorter than one frame has no frames (C division would
+  // truncate the negative numerator to 0 and report one)
+  VITS_CHECK_SHAPE(length + 2 * pad >= n_fft);
   const int frames = (length + 2 * pad - n_fft) / hop + 1;
-  VITS_CHECK_SHAPE(frames > 0);
   J = StftJobD{};
   J.x = x;
   J.window = window;
@@ -754,8 +756,8 @@ int fwd2_fblocks(const StftJobD& J) {
 
 extern "C" int64_t vits_stft_workspace(int batch, int length, int n_fft, int hop, int pad) {
   if (batch <= 0 || n_fft <= 0 || hop <= 0) return 0;
+  if (length + 2 * pad < n_fft) return 0;  // no frame fits (not one, as C division says)
   const int frames = (length + 2 * pad - n_fft) / hop + 1;
-  if (frames <= 0) return 0;
   return (int64_t)batch * frames * n_fft;
 }
 

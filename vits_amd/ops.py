@@ -1234,6 +1234,17 @@ def maximum_path_lengths(neg_cent: torch.Tensor, t_t: torch.Tensor, t_s: torch.T
 # ---------------------------------------------------------------------------
 
 
+def _stft_frames(what: str, B: int, L: int, n_fft: int, hop: int, win: int, pad: int) -> int:
+    """Frames of a reflect-padded [B, L] signal; a padded signal shorter than
+    one frame has none (torch.stft raises): refused here, so no empty tensor
+    reaches the library."""
+    if hop <= 0 or L + 2 * pad < n_fft:
+        raise _lib.VitsAmdError(
+            f"{what}: no frame fits: x [{B}, {L}] with pad {pad} gives {L + 2 * pad} samples "
+            f"for n_fft {n_fft} (hop {hop}, win {win})")
+    return (L + 2 * pad - n_fft) // hop + 1
+
+
 class _StftMag(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, window, n_fft, hop, win, pad, eps):
@@ -1241,7 +1252,7 @@ class _StftMag(torch.autograd.Function):
         x = x.contiguous().float()
         window = window.contiguous().float()
         B, L = x.shape
-        frames = (L + 2 * pad - n_fft) // hop + 1
+        frames = _stft_frames("stft_mag", B, L, n_fft, hop, win, pad)
         nb = n_fft // 2 + 1
         mag = torch.empty(B, nb, frames, device=x.device, dtype=torch.float32)
         need_grad = ctx.needs_input_grad[0]
@@ -1287,7 +1298,7 @@ class _StftMagMulti(torch.autograd.Function):
             x = x.contiguous().float()
             window = window.contiguous().float()
             B, L = x.shape
-            frames = (L + 2 * pad - n_fft) // hop + 1
+            frames = _stft_frames(f"stft_mag_multi job {i}", B, L, n_fft, hop, win, pad)
             # frame-major storage (coalesced kernel stores, layout 1); the
             # caller gets the [B, n_fft/2+1, frames] view torch.stft returns
             mag = torch.empty(B, frames, n_fft // 2 + 1, device=x.device, dtype=torch.float32)
