@@ -628,6 +628,13 @@ int vits_resblock_pair16_mean_forward(const vits_resblock_pair_desc* d, int n, i
 /* (k - 1) * dil <= 96, T % 4 == 0, 16-byte aligned x rows.               */
 int vits_resblock_pair_f32p_forward(const vits_resblock_pair_desc* d, int n, int batch,
                                     void* stream);
+/* The last split-fp32 pairs of a 32-channel stage's n branches as ONE     */
+/* launch: d[0].y receives ((pair_0 + pair_1) + pair_2) / n, bitwise the   */
+/* accumulating launches (accumulate on members > 0, post_div = n on the   */
+/* last) without their reads and writes of y.  The members share t_len,    */
+/* lengths and y; accumulate / post_div are ignored.  C = 32 only.         */
+int vits_resblock_pair_f32p_mean_forward(const vits_resblock_pair_desc* d, int n, int batch,
+                                         void* stream);
 
 /* Fused RAdam step (radam.py:35-99, the D optimizer of train_stft.py:97) */
 /* over a list of fp32 tensors, one launch per VITS_RADAM_MAX tensors.     */

@@ -364,6 +364,8 @@ _SIGS = {
         C.c_int, [C.POINTER(ResblockPairDesc), C.c_int, C.c_int, C.c_void_p]),
     "vits_resblock_pair_f32p_forward": (
         C.c_int, [C.POINTER(ResblockPairDesc), C.c_int, C.c_int, C.c_void_p]),
+    "vits_resblock_pair_f32p_mean_forward": (
+        C.c_int, [C.POINTER(ResblockPairDesc), C.c_int, C.c_int, C.c_void_p]),
     "vits_resblock_pair_kc": (
         C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vits_resblock_pair16_forward": (

@@ -136,6 +136,9 @@ _FUSED_PAIRS = True
 # Used on the 32-channel stage (C5: 0.47 -> 0.41 ms); on the 64-channel one
 # the summing kernel reaches 256 VGPRs and lost (0.61 -> 0.69 ms)
 MEAN_PAIRS16 = True
+# fp32 models: the same for the split-fp32 pairs of the 32-channel stage
+# (vits_resblock_pair_f32p_mean_forward; bitwise the accumulating launches)
+MEAN_PAIRS_F32P = True
 # 16-bit models keep the decoder's activations 16-bit in HBM (as the
 # reference's .half() model holds them): every conv of the Generator reads and
 # writes its own 16-bit type (io16), halving the stage traffic.  C5 (B=4,
@@ -305,6 +308,11 @@ class GeneratorPlan:
                 # every branch fused: one launch sums them in registers
                 ops.resblock_pair16_launch(tuple(pair_desc(j, p, xs) for j in range(nk)), B,
                                            dev, blocks[0][0][0].wdtype, mean=True)
+                continue
+            if (not io16 and not cj and 1 < nk <= 3 and MEAN_PAIRS_F32P and C == 32
+                    and all(fused[j][p][0].wdtype == ops.WDT_F32P for j in range(nk))):
+                ops.resblock_pair_launch(tuple(pair_desc(j, p, xs) for j in range(nk)), B, dev,
+                                         ops.WDT_F32P, mean=True)
                 continue
             if cj:  # (an empty group would be an empty launch)
                 ops.conv1d_launch_seq(grouped(c1_desc(j, p) for j in cj), B, dev)

@@ -585,7 +585,9 @@ class ConvTimer:
             check(lib.vits_resblock_pair_forward(arr, len(group), batch, stream.cuda_stream),
                   "vits_resblock_pair_forward")
         elif wdtype == WDT_F32P:
-            check(lib.vits_resblock_pair_f32p_forward(arr, len(group), batch, stream.cuda_stream),
+            fn = (lib.vits_resblock_pair_f32p_mean_forward if mean
+                  else lib.vits_resblock_pair_f32p_forward)
+            check(fn(arr, len(group), batch, stream.cuda_stream),
                   "vits_resblock_pair_f32p_forward")
         else:
             fn = lib.vits_resblock_pair16_mean_forward if mean else lib.vits_resblock_pair16_forward
@@ -775,19 +777,25 @@ def resblock_pair_flops(d: ResblockPairDesc, batch: int) -> int:
     return 2 * batch * T * (C_ * C_ * k + (C_ // 2) * C_ * k)
 
 
-def resblock_pair_launch(descs, batch: int, device: torch.device, wdtype: int = WDT_F32):
+def resblock_pair_launch(descs, batch: int, device: torch.device, wdtype: int = WDT_F32,
+                         mean: bool = False):
     """One launch of up to 3 independent pairs (tuple) or one pair; wdtype
     WDT_F32 (exact fp32, csrc/resblock.hip) or WDT_F32P (split fp32,
-    csrc/resblock_f32p.hip)."""
+    csrc/resblock_f32p.hip).  mean=True (WDT_F32P, 32 channels): the members'
+    mean into their common output (vits_resblock_pair_f32p_mean_forward)."""
     group = tuple(descs) if isinstance(descs, (tuple, list)) else (descs,)
     lib = _lib.load()
+    if mean and wdtype != WDT_F32P:
+        raise NotImplementedError("branch-mean launch: split-fp32 pairs only")
     if ConvTimer.active is not None:
         return ConvTimer.active.launch_pairs(lib, group, batch, device,
-                                             wdtype=WDT_F32P if wdtype == WDT_F32P else None)
+                                             wdtype=WDT_F32P if wdtype == WDT_F32P else None,
+                                             mean=mean)
     arr = (ResblockPairDesc * len(group))(*group)
     if wdtype == WDT_F32P:
-        check(lib.vits_resblock_pair_f32p_forward(arr, len(group), batch, _stream_ptr(device)),
-              "vits_resblock_pair_f32p_forward")
+        fn = (lib.vits_resblock_pair_f32p_mean_forward if mean
+              else lib.vits_resblock_pair_f32p_forward)
+        check(fn(arr, len(group), batch, _stream_ptr(device)), "vits_resblock_pair_f32p_forward")
         return
     check(lib.vits_resblock_pair_forward(arr, len(group), batch, _stream_ptr(device)),
           "vits_resblock_pair_forward")
