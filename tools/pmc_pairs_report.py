@@ -93,3 +93,9 @@ for k in sorted(agg):
           f"{a['SQ_WAIT_INST_ANY'] / max(a['2:SQ_WAVE_CYCLES'], 1):5.2f} "
           f"{a['SQ_LDS_BANK_CONFLICT'] / max(a['SQ_INSTS_LDS'], 1):7.3f} {vg + ag:4d} {lds:6d}")
     print("    raw: " + " ".join(f"{c}={v:.4g}" for c, v in sorted(a.items())))
+# effective clock (reads high on dispatches shorter than ~0.3 ms): the counter
+# runs' GRBM_GUI_ACTIVE / 8 XCDs over the trace run's kernel time
+print("\neffective clock, GRBM_GUI_ACTIVE / 8 / trace time")
+for k in sorted(agg):
+    if t[k][1]:
+        print(f"  {k:32s} {agg[k]['GRBM_GUI_ACTIVE'] / 8 / t[k][1]:5.2f} GHz")

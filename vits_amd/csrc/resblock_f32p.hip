@@ -13,7 +13,8 @@
 // (K = C/2 * k) whose own window staging, barriers and epilogue dominate
 // it (0.2-0.4 of the split-fp32 ceiling on the headline step).  Here one
 // workgroup owns a time tile of BN = NG - (k - 1) outputs and all C
-// channels; every wave computes a 64 x 64 sub-tile in both phases:
+// channels; every wave computes a 32 x 64 sub-tile (the 16-bit modes: 64 x
+// 64) in both phases:
 //   phase 1: the c1 GEMM over NG columns (the tile plus c2's (k-1)/2 halo
 //            each side; rows gate-interleaved), exactly the conv kernel's
 //            global-A loop: A fragments (hi / mid / lo planes) from the
@@ -31,11 +32,15 @@
 // The arithmetic is the two-conv path's to the bit: the same split planes,
 // the same k-step order (slab-major, then tap), the same six products per
 // fragment pair in the same order, the same gate and epilogue expressions
-// (tests/test_resblock_f32p_gpu.py checks equality).  Tiles: C = 64 ->
-// 64 x 256 (1 x 4 waves; C = 32: 32 x 256), C = 128 -> 128 x 128 (2 x 2), two workgroups per
-// CU; C = 256 -> 256 x 128 (4 x 2 waves, one 512-thread workgroup per CU:
-// the same two waves per SIMD).  Every launch holds up to 3 independent
-// pairs (the branches of a stage).
+// (tests/test_resblock_f32p_gpu.py checks equality).  Workgroup tiles: C =
+// 64 -> 64 x 256 (C = 32: 32 x 256), C = 128 -> 128 x 128, two workgroups per
+// CU; C = 256 -> 256 x 128, one per CU.  Split-fp32 at C >= 64: 32 x 64 wave
+// tiles (2 x 4, 4 x 2 and 8 x 2 waves: 512 / 512 / 1024 threads) at 128
+// VGPRs, four waves per SIMD - twice the waves of the 64 x 64 wave tile on
+// the same workgroup tile, LDS and grid, to cover the phases that issue no
+// MFMA (staging, gate, epilogue, barriers); DESIGN.md 4m, and rp_tm below
+// for the build switches that bring the 64 x 64 form back.  Every launch
+// holds up to 3 independent pairs (the branches of a stage).
 //
 // MODE 1 / 2: the same tile for a bf16 / fp16 model's 256-channel pairs
 // (vits_resblock_pair16_forward routes them here - resblock16.hip stages a
@@ -102,8 +107,40 @@ struct RpT<2> {
 __host__ __device__ constexpr int rp_npl(int mode) { return mode == 0 ? 3 : 1; }
 
 __host__ __device__ constexpr int rp_ng(int C) { return C <= 64 ? 256 : 128; }
-// threads: 4 waves (C = 64, 128), 8 waves of 64 x 64 (C = 256: 256 x 128)
-__host__ __device__ constexpr int rp_threads(int C) { return C == 256 ? 512 : 256; }
+// Wave-tile rows / 32 (TM): 2 = a 64 x 64 wave tile (64 accumulators + 96
+// double-buffered operand registers: ~200 VGPRs, two waves per SIMD), 1 =
+// 32 x 64, twice the waves on the same workgroup tile at <= 128 VGPRs (four
+// per SIMD).  Split-fp32 at C = 64 / 128 / 256: chosen per C by measurement
+// (DESIGN.md "Fused split pair: four waves per SIMD"; -DVITS_RP_TM64=2 etc.
+// rebuild the other side).  C = 32 is one 32-row wave tile; the 16-bit modes
+// keep 64 x 64 (two 8-wave workgroups measured equal there).
+#ifndef VITS_RP_TM64
+#define VITS_RP_TM64 1
+#endif
+#ifndef VITS_RP_TM128
+#define VITS_RP_TM128 1
+#endif
+#ifndef VITS_RP_TM256
+#define VITS_RP_TM256 1
+#endif
+// -DVITS_RP_OTHER_SIDE: every per-C choice flipped - the Makefile's second,
+// one-file library, through which the tests run the side that is not shipped
+#ifdef VITS_RP_OTHER_SIDE
+#define VITS_RP_SIDE(tm) (3 - (tm))
+#else
+#define VITS_RP_SIDE(tm) (tm)
+#endif
+__host__ __device__ constexpr int rp_tm(int C, int mode = 0) {
+  return C == 32     ? 1
+         : mode != 0 ? 2
+         : C == 64   ? VITS_RP_SIDE(VITS_RP_TM64)
+         : C == 128  ? VITS_RP_SIDE(VITS_RP_TM128)
+                     : VITS_RP_SIDE(VITS_RP_TM256);
+}
+// threads: (C / 32 TM) row-waves x (NG / 64) column-waves
+__host__ __device__ constexpr int rp_threads(int C, int tm) {
+  return (C / (32 * tm)) * (rp_ng(C) / 64) * 64;
+}
 // c1 channels per staged X chunk (one barrier each): 16 where two workgroups
 // share a CU (the double-buffered chunk must fit beside nothing but the G
 // planes it aliases), 64 for the one-workgroup 256-channel tile (its X
@@ -136,7 +173,11 @@ __host__ __device__ inline int rp_lds_bytes(int C, int k, int dil, int mode = 0)
 // argument): two 4-wave workgroups per CU below 256 channels, one 8-wave one
 // at 256.  (16-bit 256: two 8-wave workgroups per CU need <= 128 VGPRs and
 // spill 24; measured the same on C5, tools/r05_p256b.sh)
-__host__ __device__ constexpr int rp_occ(int C, int) { return C == 256 ? 1 : 2; }
+// The 32 x 64 wave tile: four waves per SIMD (two 8-wave workgroups, or one
+// 16-wave one at 256 channels).
+__host__ __device__ constexpr int rp_occ(int C, int, int tm) {
+  return tm == 1 && C >= 64 ? 4 : C == 256 ? 1 : 2;
+}
 
 // The gated value, rounded to fp32 once as the two-conv path stores it: the
 // product must not contract into the split's first subtraction (g - hi as
@@ -155,8 +196,29 @@ __device__ __forceinline__ float rp_max(float a, float b) {
   return r;
 }
 
-template <int C, int MODE = 0, bool MEAN = false>
-__global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_kernel(
+// A copy of a lane / thread index the compiler cannot see through.  The 32 x
+// 64 wave tile runs at the 128-register limit; what a phase derives from its
+// own copy (LDS addresses, columns, row offsets: a few integer instructions)
+// is recomputed in that phase instead of being held - or spilled - across
+// the k-loop.
+template <typename T>
+__device__ __forceinline__ T rp_fresh(T v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// A wave-uniform global address held in scalar registers, for loads of the
+// form scalar base + 32-bit lane offset (left to itself the compiler folds
+// the uniform part into a 64-bit vector address per load).
+template <typename T>
+__device__ __forceinline__ const T* rp_sbase(const T* p) {
+  uint64_t u = reinterpret_cast<uint64_t>(p);
+  asm("" : "+s"(u));
+  return (const T*)reinterpret_cast<const __attribute__((address_space(1))) T*>(u);
+}
+
+template <int C, int MODE = 0, bool MEAN = false, int TM = rp_tm(C, MODE)>
+__global__ __launch_bounds__(rp_threads(C, TM), rp_occ(C, MODE, TM)) void resblock_f32p_kernel(
     const RpGroup G) {
   typedef std::integral_constant<bool, true> edge_t;       // a tile that touches an end
   typedef std::integral_constant<bool, false> interior_t;  // all columns inside [0, L)
@@ -168,12 +230,13 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
   typedef lt lt2 __attribute__((ext_vector_type(2)));
   typedef xt xt4 __attribute__((ext_vector_type(4)));
   constexpr int H = C / 2;
-  constexpr int NT = rp_threads(C);
-  constexpr int WAVES_M = C >= 64 ? C / 64 : 1;
+  static_assert(TM == 1 || (TM == 2 && C >= 64), "wave tile rows");
+  constexpr int NT = rp_threads(C, TM);
+  constexpr int WAVES_M = C / (32 * TM);
   constexpr int WAVES_N = NT / 64 / WAVES_M;
   constexpr int NG = 64 * WAVES_N;
   static_assert(NG == rp_ng(C), "tile columns");
-  constexpr int TM = C >= 64 ? 2 : 1, TN = 2;  // 64 x 64 per wave (C = 32: 32 x 64)
+  constexpr int TN = 2;  // (32 TM) x 64 per wave
   constexpr int KC = rp_kc(C, MODE);          // c1 channels per staged chunk
   constexpr int KCP = KC + 4;           // X chunk row pitch (bf16)
   constexpr int GP = H + 8;              // G row pitch (bf16): 16-byte rows
@@ -182,6 +245,7 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
   constexpr int NU = ((KC / 4) * ((NG + 102) / 4) + NT - 1) / NT;  // staging units per thread
   typedef lt8 av_t;
   constexpr int NB = NPL == 3 ? TN : 1;  // (mid / lo B planes: split only)
+  constexpr bool REMAT = TM == 1 && C >= 64;  // (rp_fresh: the 128-register forms)
 
   // MEAN: every member on this workgroup's tile (blockIdx.z = utterance; the
   // members share t_len and lengths); else blockIdx.z = member * batch + b
@@ -202,7 +266,7 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
   const int lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: wave-uniform rows)
   const int wn = (wid % WAVES_N) * 64;
-  const int wm = (wid / WAVES_N) * 64;
+  const int wm = (wid / WAVES_N) * (32 * TM);
   const int l32 = lane & 31;
   const int lhi = lane >> 5;
 
@@ -271,15 +335,27 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
         }
     };
     // A fragments of flat step s (image [cin_pad/16][k][2][NPL][m_pad][8]):
-    // plane q, half lhi, rows wm + mi * 32 + l32
-    auto loadA = [&](const lt* wl, int64_t wstep, int m_pad, int s, int total,
+    // plane q, half lhi, rows wm + mi * 32 + l32.  The step, plane and row
+    // base are wave-uniform (a scalar address); the lane adds one 32-bit byte
+    // offset `al` (half and row: far below 2^32), so no 64-bit per-plane
+    // address lives in vector registers across the k-loop.
+    auto loadA = [&](const lt* w, uint32_t al, int64_t wstep, int m_pad, int s, int total,
                      av_t (*a)[TM]) {
-      const lt* wp = wl + (int64_t)(s < total ? s : total - 1) * wstep;
+      const lt* wp = w + (int64_t)(s < total ? s : total - 1) * wstep + (int64_t)wm * 8;
+      // (the copy keeps the offset's zero-extension beside the loads, where
+      // it folds into their scalar-base addressing)
+      const uint32_t av = REMAT ? rp_fresh(al) : al;
 #pragma unroll
       for (int q = 0; q < NPL; ++q)
 #pragma unroll
         for (int mi = 0; mi < TM; ++mi)
-          a[q][mi] = *reinterpret_cast<const av_t*>(wp + ((int64_t)q * m_pad + mi * 32) * 8);
+          if constexpr (REMAT)
+            a[q][mi] = *reinterpret_cast<const av_t*>(
+                reinterpret_cast<const char*>(rp_sbase(wp + ((int64_t)q * m_pad + mi * 32) * 8)) +
+                av);
+          else
+            a[q][mi] = *reinterpret_cast<const av_t*>(
+                reinterpret_cast<const char*>(wp + ((int64_t)q * m_pad + mi * 32) * 8) + av);
     };
 
     av_t a0[NPL][TM], a1[NPL][TM];
@@ -296,6 +372,11 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
       const float slope = p.in_slope;
       // unit u: channel quad u % (KC/4), 4-step block u / (KC/4) (a 16-lane
       // group's 8-byte LDS pieces fall on distinct banks)
+      // (xoff: bytes where KC rows of bytes stay below 2^32 given the host's
+      // C * cstride < 2^31 - one 32-bit lane offset on a scalar row address;
+      // else elements)
+      constexpr bool XB = KC * sizeof(xt) <= 2 * C;
+      constexpr uint32_t XU = XB ? (uint32_t)sizeof(xt) : 1u;
       xt4 xr[NU][4];
       uint32_t xoff[NU];
       bool xok[NU];
@@ -304,7 +385,7 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
         const int u = tid + NT * q;
         const int tt = xstart + 4 * (u / (KC / 4));
         xok[q] = u < nunits && tt >= 0 && tt < Tn;  // T % 4 == 0: a block is all in or out
-        xoff[q] = xok[q] ? 4 * (u % (KC / 4)) * p.x_cstride + tt : 0;
+        xoff[q] = xok[q] ? (uint32_t)(4 * (u % (KC / 4)) * p.x_cstride + tt) * XU : 0;
       }
       // loads issued unconditionally (a block outside reads the chunk's first
       // columns - offset 0, always inside the tensor - and is zeroed in lstore)
@@ -313,9 +394,14 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
 #pragma unroll
         for (int q = 0; q < NU; ++q) {
           if (q * NT < nunits) {
+            const uint32_t xo = REMAT ? rp_fresh(xoff[q]) : xoff[q];  // (as loadA's)
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-              xr[q][i] = *reinterpret_cast<const xt4*>(base + (int64_t)i * p.x_cstride + xoff[q]);
+            for (int i = 0; i < 4; ++i) {
+              const xt* row = base + (int64_t)i * p.x_cstride;
+              if constexpr (REMAT) row = rp_sbase(row);
+              xr[q][i] = *reinterpret_cast<const xt4*>(reinterpret_cast<const char*>(row) +
+                                                       (size_t)xo * (sizeof(xt) / XU));
+            }
           }
         }
       };
@@ -325,9 +411,10 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
       // the compare form.
       const bool xfast = interior && slope > 0.f && slope < 1.f;
       auto lstore_as = [&](lt* xs, auto edge) __attribute__((always_inline)) {
+        const int ftid = REMAT ? rp_fresh(tid) : tid;
 #pragma unroll
         for (int q = 0; q < NU; ++q) {
-          const int u = tid + NT * q;
+          const int u = ftid + NT * q;
           if (q * NT < nunits && u < nunits) {
             f32x4v v[4];
 #pragma unroll
@@ -383,12 +470,12 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
           }
         }
       };
-      const lt* wl = reinterpret_cast<const lt*>(p.w1) +
-                     ((int64_t)(lhi * NPL) * p.m_pad1 + wm + l32) * 8;
+      const lt* wl = reinterpret_cast<const lt*>(p.w1);
+      const uint32_t al = (uint32_t)((lhi * NPL) * p.m_pad1 + l32) * (uint32_t)(8 * sizeof(lt));
       const int64_t wstep = (int64_t)16 * NPL * p.m_pad1;
       const int total = S1 * k;
       const int nst = (KC / 16) * k;  // k-steps per chunk: slab-major, then tap
-      loadA(wl, wstep, p.m_pad1, 0, total, a0);
+      loadA(wl, al, wstep, p.m_pad1, 0, total, a0);
       gload(0);
       lstore(xbuf0);
       __syncthreads();
@@ -409,20 +496,20 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
         // the loads of step st + 1 pinned ahead of step st's MFMAs
         for (; st + 2 <= nst; st += 2) {
           next();
-          loadA(wl, wstep, p.m_pad1, s0 + st + 1, total, a1);
+          loadA(wl, al, wstep, p.m_pad1, s0 + st + 1, total, a1);
           loadB(xs, j, g, bh1, bm1, bl1);
           __builtin_amdgcn_sched_barrier(0);
           mma(a0, bh0, bm0, bl0);
           __builtin_amdgcn_sched_barrier(0);
           next();
-          loadA(wl, wstep, p.m_pad1, s0 + st + 2, total, a0);
+          loadA(wl, al, wstep, p.m_pad1, s0 + st + 2, total, a0);
           if (st + 2 < nst) loadB(xs, j, g, bh0, bm0, bl0);
           __builtin_amdgcn_sched_barrier(0);
           mma(a1, bh1, bm1, bl1);
           __builtin_amdgcn_sched_barrier(0);
         }
         if (st < nst) {  // odd step count: the last step, and the next chunk's A
-          loadA(wl, wstep, p.m_pad1, s0 + nst, total, a1);
+          loadA(wl, al, wstep, p.m_pad1, s0 + nst, total, a1);
           __builtin_amdgcn_sched_barrier(0);
           mma(a0, bh0, bm0, bl0);
 #pragma unroll
@@ -439,6 +526,8 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
     lt* const gs = reg;
     // (edge tiles only: the `in` select that zeroes columns outside [0, L))
     auto gate = [&](auto edge) __attribute__((always_inline)) {
+      const int flane = REMAT ? rp_fresh(lane) : lane;
+      const int l32 = flane & 31, lhi = flane >> 5;
 #pragma unroll
       for (int mi = 0; mi < TM; ++mi) {
         // the sub-tile's c1 bias + cond rows, read once for both column halves
@@ -496,8 +585,10 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
 
     // ---------------- phase 2: c2 from G --------------------------------------
     {
-      const lt* wl = reinterpret_cast<const lt*>(p.w2) +
-                     ((int64_t)(lhi * NPL) * p.m_pad2 + wm + l32) * 8;
+      const int flane = REMAT ? rp_fresh(lane) : lane;
+      const int l32 = flane & 31, lhi = flane >> 5;
+      const lt* wl = reinterpret_cast<const lt*>(p.w2);
+      const uint32_t al = (uint32_t)((lhi * NPL) * p.m_pad2 + l32) * (uint32_t)(8 * sizeof(lt));
       const int64_t wstep = (int64_t)16 * NPL * p.m_pad2;
       const int total = S2 * k;
       const lt* gl = gs + (wn + l32) * GP + 8 * lhi;
@@ -517,16 +608,16 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
           ++g;
         }
       };
-      loadA(wl, wstep, p.m_pad2, 0, total, a0);
+      loadA(wl, al, wstep, p.m_pad2, 0, total, a0);
       loadB(bh0, bm0, bl0);
       int s = 0;
       for (; s + 2 <= total; s += 2) {
-        loadA(wl, wstep, p.m_pad2, s + 1, total, a1);
+        loadA(wl, al, wstep, p.m_pad2, s + 1, total, a1);
         loadB(bh1, bm1, bl1);
         __builtin_amdgcn_sched_barrier(0);
         mma(a0, bh0, bm0, bl0);
         __builtin_amdgcn_sched_barrier(0);
-        loadA(wl, wstep, p.m_pad2, s + 2, total, a0);
+        loadA(wl, al, wstep, p.m_pad2, s + 2, total, a0);
         if (s + 2 < total) loadB(bh0, bm0, bl0);
         __builtin_amdgcn_sched_barrier(0);
         mma(a1, bh1, bm1, bl1);
@@ -547,6 +638,8 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
     const float div = MEAN ? (float)G.n : p.post_div;
     const bool last = !MEAN || br == G.n - 1;  // (MEAN: the member that stores)
     auto epilogue = [&](auto edge) __attribute__((always_inline)) {
+      const int flane = REMAT ? rp_fresh(lane) : lane;
+      const int l32 = flane & 31, lhi = flane >> 5;
 #pragma unroll
       for (int mi = 0; mi < TM; ++mi) {
         const xt* const xrow = xb + (int64_t)(wm + mi * 32) * p.x_cstride;
@@ -615,7 +708,7 @@ __global__ __launch_bounds__(rp_threads(C), rp_occ(C, MODE)) void resblock_f32p_
   }  // br
 }
 
-template <int C, int MODE = 0, bool MEAN = false>
+template <int C, int MODE = 0, bool MEAN = false, int TM = rp_tm(C, MODE)>
 int rp_launch(const RpGroup& g, hipStream_t s) {
   int lds = 0, gx = 0;
   for (int i = 0; i < g.n; ++i) {
@@ -627,8 +720,9 @@ int rp_launch(const RpGroup& g, hipStream_t s) {
     if (x > gx) gx = x;
   }
   if (lds > 160 * 1024) return VITS_E_UNSUP;
-  hipLaunchKernelGGL((resblock_f32p_kernel<C, MODE, MEAN>),
-                     dim3(gx, 1, MEAN ? g.batch : g.n * g.batch), dim3(rp_threads(C)), lds, s, g);
+  hipLaunchKernelGGL((resblock_f32p_kernel<C, MODE, MEAN, TM>),
+                     dim3(gx, 1, MEAN ? g.batch : g.n * g.batch), dim3(rp_threads(C, TM)), lds, s,
+                     g);
   return vits_launch_status();
 }
 

@@ -651,8 +651,12 @@ def resblock_pair_supported(c1: PackedConv, c2: PackedConv, T: int) -> bool:
 # k=3 -17 %, k=7 / k=11 +30..40 %.  The 32-channel stage's convs stay exact
 # fp32 as single convs (32 rows), but its pairs run split fused too
 # (engine.GeneratorPlan keeps split images beside them): vs the shipped exact
-# pair / two-conv path k=3 -2..-5 %, k=7 -25..-33 %, k=11 -34..-35 %
-F32P_PAIR_MAX_K = {32: 11, 64: 11, 128: 7, 256: 3}
+# pair / two-conv path k=3 -2..-5 %, k=7 -25..-33 %, k=11 -34..-35 %.
+# With the 32 x 64 wave tile (four waves per SIMD) C=128 k=11
+# went from +-0 to -15..-20 % and is fused too; C=256 k=7 / k=11 came to
+# +1..+10 % each alone and still lose on the whole step
+# (profiles/pairs_w8_ab.txt), so 256 stays at 3.
+F32P_PAIR_MAX_K = {32: 11, 64: 11, 128: 11, 256: 3}
 
 
 def resblock_pair_f32p_supported(c1: PackedConv, c2: PackedConv, x: torch.Tensor) -> bool:
