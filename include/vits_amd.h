@@ -46,6 +46,9 @@
  *                            for a whole batch in call order
  *   vits_pack_pcm            the segment concatenation of VITSWrap.speaking
  *                            (vits_wrap.py:198,212-214), on the device
+ *   vits_*_rows              the four above with the speed, the ratio, the
+ *                            volume and the tail per row: requests with
+ *                            different controls behind one graph replay
  */
 #ifndef VITS_AMD_H
 #define VITS_AMD_H
@@ -261,6 +264,23 @@ int vits_draw_starts(const float* logw, int64_t logw_bstride, const int32_t* x_l
                      float rate, int half_round, int channels, int64_t noise_len,
                      const uint32_t* pool, int pool_n, const int32_t* n_rows, int batch,
                      int64_t* starts, int32_t* meta, void* stream);
+
+/* Per-row speed: vits_expand_durations / vits_draw_starts with row b's rate */
+/* read on the device from rates[b] (fp32 [batch]) in place of the scalar,  */
+/* so that one captured graph serves every mix of speeds.  The arithmetic   */
+/* is the scalar entry points' (one fp32 multiply, then the half_round      */
+/* roundings): a row with rates[b] == rate is bit for bit the scalar call.  */
+int vits_expand_durations_rows(const float* logw, int64_t logw_bstride, const int32_t* x_len,
+                               int t_x, const float* rates, int half_round, const float* m,
+                               const float* s, int64_t ms_bstride, int32_t ms_cstride,
+                               const float* noise, int noise_mode, const int32_t* noise_start,
+                               int64_t noise_len, float noise_scale, float* z, int batch,
+                               int channels, int t_y, int32_t* lens, const int32_t* stage_mult,
+                               int n_stage, void* stream);
+int vits_draw_starts_rows(const float* logw, int64_t logw_bstride, const int32_t* x_len, int t_x,
+                          const float* rates, int half_round, int channels, int64_t noise_len,
+                          const uint32_t* pool, int pool_n, const int32_t* n_rows, int batch,
+                          int64_t* starts, int32_t* meta, void* stream);
 
 int vits_conv_post_tanh(const float* x, int64_t x_bstride, int32_t x_cstride, const float* w,
                         float* y, int batch, int channels, int t_len, int ksize, void* stream);
@@ -835,6 +855,42 @@ int vits_pack_pcm(const int16_t* rows, int64_t bstride, int cap, const int32_t* 
                   const int32_t* up, const int32_t* down, int n_passes, int tail,
                   const int32_t* n_rows, int batch, int32_t* offsets, int16_t* out,
                   int64_t out_cap, void* stream);
+
+/* ---------------------------------------------------------------------- */
+/* Per-row output stage: the rows of one launch belong to different         */
+/* requests, each with its own pitch, output rate, volume and tail.         */
+/* vits_resample_poly_rows is vits_resample_poly with the ratio, filter and */
+/* volume of row b taken from rows[b] (a HOST array of `batch` records,     */
+/* copied into the kernel arguments: the call keeps no pointer to it):      */
+/* up / down reduced, half_len = 10 * max(up, down), table [up][table_k]    */
+/* with table_k = ceil((2 * half_len + 1) / up) as above, on the device; up */
+/* == down == 1 is the copy (table ignored).  Every output sample is        */
+/* computed exactly as vits_resample_poly computes it for that ratio.  The  */
+/* row length is lens[b] * len_scale (device int32 [batch], required); out  */
+/* / pcm is [batch][out_cap] for ONE shared out_cap, each row zero from its */
+/* own n_out = ceil(n_in * up / down) (clamped to out_cap) to out_cap;      */
+/* out_lens (NULL = skip) receives n_out.  batch <= 64.                     */
+/* ---------------------------------------------------------------------- */
+typedef struct {
+  const float* table; /* device, [up][table_k]; NULL for up == down == 1 */
+  int32_t up, down, half_len, table_k;
+  float volume;       /* int16 output only */
+  int32_t reserved;
+} vits_post_row;
+int vits_resample_poly_rows(const void* x, int x_dtype, int64_t x_bstride, int x_cap,
+                            const int32_t* lens, int len_scale, const vits_post_row* rows,
+                            float* out, int16_t* pcm, int64_t out_bstride, int out_cap,
+                            int32_t* out_lens, int batch, void* stream);
+
+/* vits_pack_pcm with per-row ratios and tails: up / down are HOST int32    */
+/* [batch][2] (1 / 1 in a slot the row does not use), tail HOST int32       */
+/* [batch] (>= 0); n_out[b] = y_len[b] * hop through ceil(n * up[b][i] /    */
+/* down[b][i]), i = 0, 1; offsets[b + 1] = offsets[b] + n_out[b] + tail[b]. */
+/* Everything else as vits_pack_pcm.                                        */
+int vits_pack_pcm_rows(const int16_t* rows, int64_t bstride, int cap, const int32_t* y_len,
+                       int hop, const int32_t* up, const int32_t* down, const int32_t* tail,
+                       const int32_t* n_rows, int batch, int32_t* offsets, int16_t* out,
+                       int64_t out_cap, void* stream);
 
 /* library introspection */
 const char* vits_amd_version(void);

@@ -245,6 +245,19 @@ class SnormLayer(C.Structure):
     ]
 
 
+class PostRow(C.Structure):
+    """include/vits_amd.h vits_post_row (one row of vits_resample_poly_rows)."""
+    _fields_ = [
+        ("table", C.c_void_p),
+        ("up", C.c_int32),
+        ("down", C.c_int32),
+        ("half_len", C.c_int32),
+        ("table_k", C.c_int32),
+        ("volume", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
 _SIGS = {
     "vits_conv1d_forward": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_void_p]),
     "vits_conv1d_forward_seq": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_void_p]),
@@ -435,6 +448,27 @@ _SIGS = {
         C.c_int,
         [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
          C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    ),
+    "vits_expand_durations_rows": (
+        C.c_int,
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+         C.c_int64, C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
+         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    ),
+    "vits_draw_starts_rows": (
+        C.c_int,
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64,
+         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "vits_resample_poly_rows": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.POINTER(PostRow),
+         C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p],
+    ),
+    "vits_pack_pcm_rows": (
+        C.c_int,
+        [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     ),
     "vits_amd_version": (C.c_char_p, []),
     "vits_amd_device_arch": (C.c_int, [C.c_char_p, C.c_int]),

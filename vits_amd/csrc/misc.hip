@@ -226,10 +226,10 @@ __device__ __forceinline__ int ed_masked_draw(const uint32_t* __restrict__ pool,
 
 __global__ __launch_bounds__(256) void expand_durations_kernel(
     const float* __restrict__ logw, int64_t logw_bstride, const int32_t* __restrict__ x_len,
-    int t_x, float rate, int half_round, const float* __restrict__ m, const float* __restrict__ s,
-    int64_t ms_bstride, int ms_cstride, const float* __restrict__ noise, int noise_mode,
-    const int32_t* __restrict__ noise_start, int64_t noise_len, float noise_scale,
-    float* __restrict__ z, int channels, int t_y, int batch, int32_t* __restrict__ lens,
+    int t_x, float rate, const float* __restrict__ rates, int half_round,
+    const float* __restrict__ m, const float* __restrict__ s, int64_t ms_bstride, int ms_cstride,
+    const float* __restrict__ noise, int noise_mode, const int32_t* __restrict__ noise_start,
+    int64_t noise_len, float noise_scale, float* __restrict__ z, int channels, int t_y, int batch, int32_t* __restrict__ lens,
     const EdStages st) {
   __shared__ int cum[ED_MAX_TX];
   __shared__ int part[256];
@@ -239,8 +239,8 @@ __global__ __launch_bounds__(256) void expand_durations_kernel(
   const int nx = x_len ? min(x_len[b], t_x) : t_x;
   // 1) integer durations, their scan and y_len
   int total;
-  const int y_len = ed_scan_durations(logw + (int64_t)b * logw_bstride, nx, t_x, rate, half_round,
-                                      cum, part, total);
+  const int y_len = ed_scan_durations(logw + (int64_t)b * logw_bstride, nx, t_x,
+                                      rates ? rates[b] : rate, half_round, cum, part, total);
   if (blockIdx.x == 0 && tid < st.n) lens[tid * batch + b] = y_len * st.mult[tid];
   // 2) token of each frame of this workgroup: first x with cum[x] > t
   const int t0 = blockIdx.x * ED_T;
@@ -332,9 +332,10 @@ __global__ __launch_bounds__(256) void expand_durations_kernel(
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void draw_starts_kernel(
     const float* __restrict__ logw, int64_t logw_bstride, const int32_t* __restrict__ x_len,
-    int t_x, float rate, int half_round, int channels, int64_t noise_len,
-    const uint32_t* __restrict__ pool, int pool_n, const int32_t* __restrict__ n_rows_p,
-    int batch, int64_t* __restrict__ starts, int32_t* __restrict__ meta) {
+    int t_x, float rate, const float* __restrict__ rates, int half_round, int channels,
+    int64_t noise_len, const uint32_t* __restrict__ pool, int pool_n,
+    const int32_t* __restrict__ n_rows_p, int batch, int64_t* __restrict__ starts,
+    int32_t* __restrict__ meta) {
   __shared__ int cum[ED_MAX_TX];
   __shared__ int part[256];
   const int n_rows = n_rows_p ? min(max(*n_rows_p, 0), batch) : batch;
@@ -342,8 +343,8 @@ __global__ __launch_bounds__(256) void draw_starts_kernel(
   for (int b = 0; b < batch; ++b) {
     const int nx = x_len ? min(x_len[b], t_x) : t_x;
     int total;
-    const int y_len = ed_scan_durations(logw + (int64_t)b * logw_bstride, nx, t_x, rate,
-                                        half_round, cum, part, total);
+    const int y_len = ed_scan_durations(logw + (int64_t)b * logw_bstride, nx, t_x,
+                                        rates ? rates[b] : rate, half_round, cum, part, total);
     __syncthreads();  // cum / part are rewritten for the next row
     if (threadIdx.x == 0) {
       int64_t start = 0;
@@ -519,14 +520,13 @@ extern "C" int vits_expand_prior(const float* attn, const float* m, const float*
   return vits_launch_status();
 }
 
-extern "C" int vits_expand_durations(const float* logw, int64_t logw_bstride,
-                                     const int32_t* x_len, int t_x, float rate, int half_round,
-                                     const float* m, const float* s, int64_t ms_bstride,
-                                     int32_t ms_cstride, const float* noise, int noise_mode,
-                                     const int32_t* noise_start, int64_t noise_len,
-                                     float noise_scale, float* z,
-                                     int batch, int channels, int t_y, int32_t* lens,
-                                     const int32_t* stage_mult, int n_stage, void* stream) {
+// rates == nullptr: every row runs at `rate`; else row b at rates[b] (device)
+static int ed_launch(const float* logw, int64_t logw_bstride, const int32_t* x_len, int t_x,
+                     float rate, const float* rates, int half_round, const float* m,
+                     const float* s, int64_t ms_bstride, int32_t ms_cstride, const float* noise,
+                     int noise_mode, const int32_t* noise_start, int64_t noise_len,
+                     float noise_scale, float* z, int batch, int channels, int t_y, int32_t* lens,
+                     const int32_t* stage_mult, int n_stage, void* stream) {
   VITS_CHECK_ARG(logw && m && s && noise && z && lens && batch > 0 && channels > 0 && t_y > 0 &&
                  t_x > 0);
   VITS_CHECK_ARG(n_stage >= 1 && n_stage <= ED_MAX_STAGES && (n_stage == 1 || stage_mult));
@@ -539,9 +539,51 @@ extern "C" int vits_expand_durations(const float* logw, int64_t logw_bstride,
   for (int i = 0; i < ED_MAX_STAGES; ++i) st.mult[i] = i < n_stage ? (stage_mult ? stage_mult[i] : 1) : 0;
   dim3 grid((t_y + ED_T - 1) / ED_T, batch);
   hipLaunchKernelGGL(expand_durations_kernel, grid, dim3(256), 0, as_stream(stream), logw,
-                     logw_bstride, x_len, t_x, rate, half_round, m, s, ms_bstride, ms_cstride,
-                     noise, noise_mode, noise_start, noise_len, noise_scale, z, channels, t_y,
-                     batch, lens, st);
+                     logw_bstride, x_len, t_x, rate, rates, half_round, m, s, ms_bstride,
+                     ms_cstride, noise, noise_mode, noise_start, noise_len, noise_scale, z,
+                     channels, t_y, batch, lens, st);
+  return vits_launch_status();
+}
+
+extern "C" int vits_expand_durations(const float* logw, int64_t logw_bstride,
+                                     const int32_t* x_len, int t_x, float rate, int half_round,
+                                     const float* m, const float* s, int64_t ms_bstride,
+                                     int32_t ms_cstride, const float* noise, int noise_mode,
+                                     const int32_t* noise_start, int64_t noise_len,
+                                     float noise_scale, float* z,
+                                     int batch, int channels, int t_y, int32_t* lens,
+                                     const int32_t* stage_mult, int n_stage, void* stream) {
+  return ed_launch(logw, logw_bstride, x_len, t_x, rate, nullptr, half_round, m, s, ms_bstride,
+                   ms_cstride, noise, noise_mode, noise_start, noise_len, noise_scale, z, batch,
+                   channels, t_y, lens, stage_mult, n_stage, stream);
+}
+
+extern "C" int vits_expand_durations_rows(const float* logw, int64_t logw_bstride,
+                                          const int32_t* x_len, int t_x, const float* rates,
+                                          int half_round, const float* m, const float* s,
+                                          int64_t ms_bstride, int32_t ms_cstride,
+                                          const float* noise, int noise_mode,
+                                          const int32_t* noise_start, int64_t noise_len,
+                                          float noise_scale, float* z, int batch, int channels,
+                                          int t_y, int32_t* lens, const int32_t* stage_mult,
+                                          int n_stage, void* stream) {
+  VITS_CHECK_ARG(rates);
+  return ed_launch(logw, logw_bstride, x_len, t_x, 1.0f, rates, half_round, m, s, ms_bstride,
+                   ms_cstride, noise, noise_mode, noise_start, noise_len, noise_scale, z, batch,
+                   channels, t_y, lens, stage_mult, n_stage, stream);
+}
+
+static int ds_launch(const float* logw, int64_t logw_bstride, const int32_t* x_len, int t_x,
+                     float rate, const float* rates, int half_round, int channels,
+                     int64_t noise_len, const uint32_t* pool, int pool_n, const int32_t* n_rows,
+                     int batch, int64_t* starts, int32_t* meta, void* stream) {
+  VITS_CHECK_ARG(logw && pool && starts && meta && batch > 0 && channels > 0 && t_x > 0 &&
+                 pool_n > 0 && noise_len > 0);
+  VITS_CHECK_ARG((reinterpret_cast<uintptr_t>(starts) & 7) == 0);
+  VITS_CHECK_SHAPE(t_x <= ED_MAX_TX && batch <= 1024 && logw_bstride >= t_x);
+  hipLaunchKernelGGL(draw_starts_kernel, dim3(1), dim3(256), 0, as_stream(stream), logw,
+                     logw_bstride, x_len, t_x, rate, rates, half_round, channels, noise_len, pool,
+                     pool_n, n_rows, batch, starts, meta);
   return vits_launch_status();
 }
 
@@ -550,14 +592,18 @@ extern "C" int vits_draw_starts(const float* logw, int64_t logw_bstride, const i
                                 int64_t noise_len, const uint32_t* pool, int pool_n,
                                 const int32_t* n_rows, int batch, int64_t* starts, int32_t* meta,
                                 void* stream) {
-  VITS_CHECK_ARG(logw && pool && starts && meta && batch > 0 && channels > 0 && t_x > 0 &&
-                 pool_n > 0 && noise_len > 0);
-  VITS_CHECK_ARG((reinterpret_cast<uintptr_t>(starts) & 7) == 0);
-  VITS_CHECK_SHAPE(t_x <= ED_MAX_TX && batch <= 1024 && logw_bstride >= t_x);
-  hipLaunchKernelGGL(draw_starts_kernel, dim3(1), dim3(256), 0, as_stream(stream), logw,
-                     logw_bstride, x_len, t_x, rate, half_round, channels, noise_len, pool, pool_n,
-                     n_rows, batch, starts, meta);
-  return vits_launch_status();
+  return ds_launch(logw, logw_bstride, x_len, t_x, rate, nullptr, half_round, channels, noise_len,
+                   pool, pool_n, n_rows, batch, starts, meta, stream);
+}
+
+extern "C" int vits_draw_starts_rows(const float* logw, int64_t logw_bstride,
+                                     const int32_t* x_len, int t_x, const float* rates,
+                                     int half_round, int channels, int64_t noise_len,
+                                     const uint32_t* pool, int pool_n, const int32_t* n_rows,
+                                     int batch, int64_t* starts, int32_t* meta, void* stream) {
+  VITS_CHECK_ARG(rates);
+  return ds_launch(logw, logw_bstride, x_len, t_x, 1.0f, rates, half_round, channels, noise_len,
+                   pool, pool_n, n_rows, batch, starts, meta, stream);
 }
 
 extern "C" int vits_conv_post_tanh(const float* x, int64_t x_bstride, int32_t x_cstride,

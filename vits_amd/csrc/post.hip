@@ -38,15 +38,17 @@ __device__ __forceinline__ void post_st(int16_t* p, int64_t i, float v, float vo
   p[i] = (int16_t)(int)s;
 }
 
+// Output sample blockIdx.x * 256 + threadIdx.x of row b = blockIdx.y, whose
+// input length is n_in before clamping: the one place the arithmetic of the
+// output stage lives (the uniform and the per-row kernel both call it).
 // table == nullptr: up == down == 1, out[n] = x[n] (the copy / the epilogue alone)
 template <typename XT, typename OT>
-__global__ __launch_bounds__(256) void post_resample_kernel(
-    const XT* __restrict__ x, int64_t x_bstride, int x_cap, const int32_t* __restrict__ lens,
-    int len_scale, int n_host, const float* __restrict__ table, int K, int up, int down,
-    int half_len, OT* __restrict__ out, int64_t out_bstride, int out_cap, float volume,
+__device__ __forceinline__ void post_row_sample(
+    const XT* __restrict__ x, int64_t x_bstride, int x_cap, int64_t n_in,
+    const float* __restrict__ table, int K, int up, int down, int half_len,
+    OT* __restrict__ out, int64_t out_bstride, int out_cap, float volume,
     int32_t* __restrict__ out_lens) {
   const int b = blockIdx.y;
-  int64_t n_in = lens ? (int64_t)lens[b] * len_scale : (int64_t)n_host;
   n_in = min(max(n_in, (int64_t)0), (int64_t)x_cap);
   const int64_t n_out = min((n_in * up + down - 1) / down, (int64_t)out_cap);
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -68,6 +70,59 @@ __global__ __launch_bounds__(256) void post_resample_kernel(
     }
   }
   post_st(out + (int64_t)b * out_bstride, n, acc, volume);
+}
+
+template <typename XT, typename OT>
+__global__ __launch_bounds__(256) void post_resample_kernel(
+    const XT* __restrict__ x, int64_t x_bstride, int x_cap, const int32_t* __restrict__ lens,
+    int len_scale, int n_host, const float* __restrict__ table, int K, int up, int down,
+    int half_len, OT* __restrict__ out, int64_t out_bstride, int out_cap, float volume,
+    int32_t* __restrict__ out_lens) {
+  const int64_t n_in = lens ? (int64_t)lens[blockIdx.y] * len_scale : (int64_t)n_host;
+  post_row_sample(x, x_bstride, x_cap, n_in, table, K, up, down, half_len, out, out_bstride,
+                  out_cap, volume, out_lens);
+}
+
+// ---------------------------------------------------------------------------
+// Per-row form: one launch over [batch][x_cap] in which every row has its own
+// ratio, filter and volume (a group of requests with different pitch, output
+// rate and volume behind one graph replay).  The descriptors travel by value
+// in the kernel arguments; row b = blockIdx.y is uniform per workgroup, so
+// its descriptor is read with scalar loads and the sample loop is the uniform
+// kernel's.  The grid covers the shared out_cap: a row is zero from its own
+// n_out on.
+// ---------------------------------------------------------------------------
+constexpr int PR_MAX_BATCH = 64;
+struct PostRows {
+  vits_post_row r[PR_MAX_BATCH];
+};
+
+template <typename XT, typename OT>
+__global__ __launch_bounds__(256) void post_resample_rows_kernel(
+    const XT* __restrict__ x, int64_t x_bstride, int x_cap, const int32_t* __restrict__ lens,
+    int len_scale, const PostRows rows, OT* __restrict__ out, int64_t out_bstride, int out_cap,
+    int32_t* __restrict__ out_lens) {
+  const vits_post_row& d = rows.r[blockIdx.y];
+  post_row_sample(x, x_bstride, x_cap, (int64_t)lens[blockIdx.y] * len_scale, d.table, d.table_k,
+                  d.up, d.down, d.half_len, out, out_bstride, out_cap, d.volume, out_lens);
+}
+
+template <typename XT>
+int post_rows_launch(const void* x, int64_t x_bstride, int x_cap, const int32_t* lens,
+                     int len_scale, const PostRows& rows, float* out, int16_t* pcm,
+                     int64_t out_bstride, int out_cap, int32_t* out_lens, int batch,
+                     hipStream_t s) {
+  const dim3 grid((out_cap + 255) / 256, batch);
+  const XT* xp = reinterpret_cast<const XT*>(x);
+  if (pcm)
+    hipLaunchKernelGGL((post_resample_rows_kernel<XT, int16_t>), grid, dim3(256), 0, s, xp,
+                       x_bstride, x_cap, lens, len_scale, rows, pcm, out_bstride, out_cap,
+                       out_lens);
+  else
+    hipLaunchKernelGGL((post_resample_rows_kernel<XT, float>), grid, dim3(256), 0, s, xp,
+                       x_bstride, x_cap, lens, len_scale, rows, out, out_bstride, out_cap,
+                       out_lens);
+  return vits_launch_status();
 }
 
 template <typename XT>
@@ -182,7 +237,120 @@ __global__ __launch_bounds__(256) void pack_pcm_kernel(
   }
 }
 
+// Per-row form of the pack: row b has its own pass ratios (always
+// PK_MAX_PASSES of them, 1 / 1 where it has fewer) and its own tail.
+struct PackRows {
+  int32_t up[PK_MAX_BATCH][PK_MAX_PASSES];
+  int32_t down[PK_MAX_BATCH][PK_MAX_PASSES];
+  int32_t tail[PK_MAX_BATCH];
+};
+
+__device__ __forceinline__ int64_t pack_rows_len(int32_t frames, int hop, const PackRows& pr,
+                                                 int r) {
+  int64_t n = (int64_t)max(frames, 0) * hop;
+  for (int i = 0; i < PK_MAX_PASSES; ++i) n = (n * pr.up[r][i] + pr.down[r][i] - 1) / pr.down[r][i];
+  return n;
+}
+
+__global__ __launch_bounds__(256) void pack_pcm_rows_kernel(
+    const int16_t* __restrict__ rows, int64_t bstride, int cap, const int32_t* __restrict__ y_len,
+    int hop, const PackRows pr, const int32_t* __restrict__ n_rows_p, int batch,
+    int32_t* __restrict__ offsets, int16_t* __restrict__ stream, int64_t stream_cap) {
+  const int b = blockIdx.y;
+  const int n_rows = n_rows_p ? min(max(*n_rows_p, 0), batch) : batch;
+  if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
+    int64_t off = 0;
+    offsets[0] = 0;
+    for (int r = 0; r < batch; ++r) {
+      if (r < n_rows) off += pack_rows_len(y_len[r], hop, pr, r) + pr.tail[r];
+      offsets[r + 1] = (int32_t)min(off, (int64_t)INT32_MAX);
+    }
+  }
+  if (b >= n_rows) return;
+  int64_t off = 0;
+  for (int r = 0; r < b; ++r) off += pack_rows_len(y_len[r], hop, pr, r) + pr.tail[r];
+  const int64_t n_out = pack_rows_len(y_len[b], hop, pr, b);
+  const int tail = pr.tail[b];
+  const int16_t* src = rows + (int64_t)b * bstride;
+  for (int k = 0; k < PK_T / 256; ++k) {
+    const int64_t i = (int64_t)blockIdx.x * PK_T + k * 256 + threadIdx.x;
+    if (i >= n_out + tail || off + i >= stream_cap) break;
+    stream[off + i] = (i < n_out && i < cap) ? src[i] : (int16_t)0;
+  }
+}
+
 }  // namespace
+
+extern "C" int vits_resample_poly_rows(const void* x, int x_dtype, int64_t x_bstride, int x_cap,
+                                       const int32_t* lens, int len_scale,
+                                       const vits_post_row* rows, float* out, int16_t* pcm,
+                                       int64_t out_bstride, int out_cap, int32_t* out_lens,
+                                       int batch, void* stream) {
+  VITS_CHECK_ARG(x && lens && rows && batch > 0 && x_cap > 0 && out_cap > 0 && len_scale >= 1);
+  VITS_CHECK_ARG((out != nullptr) != (pcm != nullptr));
+  VITS_CHECK_ARG(x_dtype == VITS_DT_F32 || x_dtype == VITS_DT_F16 || x_dtype == VITS_DT_BF16);
+  VITS_CHECK_SHAPE(batch <= PR_MAX_BATCH && x_bstride >= x_cap && out_bstride >= out_cap);
+  PostRows pr;
+  for (int b = 0; b < PR_MAX_BATCH; ++b) {
+    vits_post_row& d = pr.r[b];
+    if (b >= batch) {
+      d = vits_post_row{nullptr, 1, 1, 0, 0, 1.0f, 0};
+      continue;
+    }
+    d = rows[b];
+    d.reserved = 0;
+    VITS_CHECK_ARG(d.up >= 1 && d.down >= 1);
+    if (d.up == 1 && d.down == 1) {
+      d.table = nullptr;  // scipy returns a copy: no filter
+      d.half_len = d.table_k = 0;
+    } else {
+      // the phase table must be the one of this row's ratio (see post_dispatch)
+      VITS_CHECK_ARG(d.table);
+      VITS_CHECK_SHAPE(d.half_len == 10 * (d.up > d.down ? d.up : d.down));
+      VITS_CHECK_SHAPE(d.table_k == (2 * d.half_len + d.up) / d.up);
+    }
+  }
+  const hipStream_t s = as_stream(stream);
+  switch (x_dtype) {
+    case VITS_DT_F16:
+      return post_rows_launch<_Float16>(x, x_bstride, x_cap, lens, len_scale, pr, out, pcm,
+                                        out_bstride, out_cap, out_lens, batch, s);
+    case VITS_DT_BF16:
+      return post_rows_launch<__bf16>(x, x_bstride, x_cap, lens, len_scale, pr, out, pcm,
+                                      out_bstride, out_cap, out_lens, batch, s);
+    default:
+      return post_rows_launch<float>(x, x_bstride, x_cap, lens, len_scale, pr, out, pcm,
+                                     out_bstride, out_cap, out_lens, batch, s);
+  }
+}
+
+extern "C" int vits_pack_pcm_rows(const int16_t* rows, int64_t bstride, int cap,
+                                  const int32_t* y_len, int hop, const int32_t* up,
+                                  const int32_t* down, const int32_t* tail, const int32_t* n_rows,
+                                  int batch, int32_t* offsets, int16_t* out, int64_t out_cap,
+                                  void* stream) {
+  VITS_CHECK_ARG(rows && y_len && offsets && out && up && down && tail && batch > 0 && cap > 0 &&
+                 hop >= 1 && out_cap > 0);
+  VITS_CHECK_SHAPE(batch <= PK_MAX_BATCH && bstride >= cap);
+  PackRows pr;
+  int tail_max = 0;
+  for (int b = 0; b < PK_MAX_BATCH; ++b) {
+    for (int i = 0; i < PK_MAX_PASSES; ++i) {
+      pr.up[b][i] = b < batch ? up[b * PK_MAX_PASSES + i] : 1;
+      pr.down[b][i] = b < batch ? down[b * PK_MAX_PASSES + i] : 1;
+      VITS_CHECK_ARG(pr.up[b][i] >= 1 && pr.down[b][i] >= 1);
+    }
+    pr.tail[b] = b < batch ? tail[b] : 0;
+    VITS_CHECK_ARG(pr.tail[b] >= 0);
+    tail_max = pr.tail[b] > tail_max ? pr.tail[b] : tail_max;
+  }
+  const int64_t n_max = (int64_t)cap + tail_max;  // the longest row a buffer row can hold
+  VITS_CHECK_SHAPE(n_max <= INT32_MAX);
+  const dim3 grid((unsigned)((n_max + PK_T - 1) / PK_T), batch);
+  hipLaunchKernelGGL(pack_pcm_rows_kernel, grid, dim3(256), 0, as_stream(stream), rows, bstride,
+                     cap, y_len, hop, pr, n_rows, batch, offsets, out, out_cap);
+  return vits_launch_status();
+}
 
 extern "C" int vits_pack_pcm(const int16_t* rows, int64_t bstride, int cap, const int32_t* y_len,
                              int hop, const int32_t* up, const int32_t* down, int n_passes,

@@ -12,6 +12,8 @@ from __future__ import annotations
 
 import os
 import sys
+from dataclasses import dataclass
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
@@ -19,6 +21,18 @@ import torch
 from . import ops, utils
 from .commons import infer_path
 from .export import load_model
+
+
+@dataclass
+class PcmRequest:
+    """One request of EmoVITS.infer_pcm_requests: ``items`` = [(spkid, text
+    [N, c], emo), ...] and the controls of infer_pcm_batch, its own."""
+    items: Sequence
+    duration_rate: float = 1.0
+    pitch: float = 1.0
+    sampling_rate: Optional[int] = None
+    volume: float = 1.0
+    tail_silence: float = 0.0
 
 
 class EmoVITS(object):
@@ -29,7 +43,8 @@ class EmoVITS(object):
         length and the path computed on the device, no host sync before the
         waveform copy), graphs cached per (text bucket, frame bucket), at
         most ``max_graphs`` (the batched graphs of infer_batch /
-        infer_pcm_batch included); graph=False: the reference's eager
+        infer_pcm_batch and the rate-free ones of infer_pcm_requests
+        included); graph=False: the reference's eager
         sequence (infer_p1 -> host durations -> infer_p2)."""
         self.loglv = loglv
         self.graph_cache = int(graph_cache)
@@ -383,6 +398,94 @@ class EmoVITS(object):
         torch.cat(words, out=out[2 * (B + 1):2 * (3 * B + 2)].view(torch.int32))
         return out
 
+    # -- mixed requests: rows with their own speed, pitch, rate, volume, tail ------
+    def infer_pcm_requests(self, requests):
+        """infer_pcm_batch for several requests at once, each a PcmRequest
+        with its own controls: one (pcm, offsets, emos, n_model) per request,
+        what ``infer_pcm_batch(r.items, **controls)`` returns for it when the
+        calls are made in order, with numpy's generator left in the same
+        state.  Order of numpy draws: every request's emotion lookups first,
+        in request and item order, then the noise draws in row order
+        (_resolve_items' rule over the whole call; the in-order loop's
+        exactly when the emotions are tensors or explicit ids).
+
+        The rows of all requests are flattened in order and cut into groups
+        of at most MAX_BATCH.  A group is ONE replay of a rate-free batched
+        graph (the speeds are a device input, so one graph per (batch, text,
+        frame) bucket serves every speed and pitch), then as many per-row
+        post launches as the row with the most passes needs
+        (ops.resample_rows: a row with fewer passes copies in the slot it
+        does not use), the per-row pack (ops.pack_pcm_rows) and ONE
+        device-to-host copy.  A group of one row, a CPU device or graph=False
+        run infer_pcm's path per row."""
+        requests = list(requests)
+        rows, spans = [], []  # per row: (text, spkid, emo, request); per request: (lo, hi, emos)
+        for r in requests:
+            texts, spkids, emos = self._resolve_items(r.items)
+            spans.append((len(rows), len(rows) + len(texts), emos))
+            rows += [(t, s, e, r) for t, s, e in zip(texts, spkids, emos)]
+        pcms, n_model = [], []
+        for lo, hi in self._groups(len(rows)):
+            group = rows[lo:hi]
+            ctl = [(self.sampling_rate if r.sampling_rate is None else int(r.sampling_rate), r)
+                   for _, _, _, r in group]
+            if hi - lo == 1 or not self._batchable([t for t, _, _, _ in group]):
+                for (text, spkid, emo, r), (sr, _) in zip(group, ctl):
+                    x_length, text_t, sid = self._one_tensors(spkid, text)
+                    pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, r.duration_rate,
+                                                 r.pitch, sr, r.volume, r.tail_silence)
+                    pcms.append(pcm)
+                    n_model.append(n)
+                continue
+            passes = [self._post_passes(r.pitch, sr) for sr, r in ctl]
+            volumes = [r.volume for _, r in ctl]
+            tails = [int(r.tail_silence * sr) if r.tail_silence > 0 else 0 for sr, r in ctl]
+            (pcm, offs), y = self._infer_graph_batch(
+                [t for t, _, _, _ in group], [e for _, _, e, _ in group],
+                [s for _, s, _, _ in group], None, rates=[r.duration_rate for _, r in ctl],
+                post=lambda wav, y_len, n_rows, words: self._post_pack_rows(
+                    wav, y_len, n_rows, words, passes, volumes, tails))
+            pcms += [pcm[int(offs[i]):int(offs[i + 1])] for i in range(hi - lo)]
+            n_model += [n * self.hop_size for n in y]
+        out = []
+        for lo, hi, emos in spans:
+            offsets = np.cumsum([0] + [len(p) for p in pcms[lo:hi]]).astype(np.int64)
+            pcm = np.concatenate(pcms[lo:hi]) if hi > lo else np.zeros(0, dtype=np.int16)
+            out.append((pcm, offsets, emos, n_model[lo:hi]))
+        return out
+
+    def _post_pack_rows(self, wav, y_len, n_rows, words, passes, volumes, tails):
+        """_post_pack with per-row controls: ``passes`` / ``volumes`` /
+        ``tails`` of the group's rows (the padding rows of the bucket copy at
+        volume 1 with no tail).  max(1, most passes of a row) launches of
+        ops.resample_rows: the last one writes the PCM, the ones before it
+        fp32 and the lengths; a row's passes fill the first slots, (1, 1)
+        the rest, which leaves its samples as they are."""
+        B = wav.shape[0]
+        pad = B - len(passes)
+        passes, volumes, tails = passes + [[]] * pad, volumes + [1.0] * pad, tails + [0] * pad
+        n_launch = max(1, max(len(p) for p in passes))
+        x, lengths, scale = wav, y_len, self.hop_size
+        caps = [wav.shape[1]] * B
+        for i in range(n_launch):
+            ratios = [p[i] if i < len(p) else (1, 1) for p in passes]
+            caps = [ops.resample_out_len(c, u, d) for c, (u, d) in zip(caps, ratios)]
+            if i == n_launch - 1:
+                break
+            mid = torch.empty(B, max(1, max(caps)), device=wav.device, dtype=torch.float32)
+            nxt = torch.empty(B, device=wav.device, dtype=torch.int32)
+            ops.resample_rows(x, ratios, lengths=lengths, length_scale=scale, out=mid,
+                              out_lengths=nxt)
+            x, lengths, scale = mid, nxt, 1
+        pcm = torch.empty(B, max(1, max(caps) + max(tails)), device=wav.device, dtype=torch.int16)
+        ops.resample_rows(x, ratios, lengths=lengths, length_scale=scale, volumes=volumes,
+                          pcm=True, out=pcm)
+        header = -(-2 * (3 * B + 2) // 8) * 8
+        out, _, _ = ops.pack_pcm_rows(pcm, y_len, self.hop_size, passes, tails, n_rows=n_rows,
+                                      header=header)
+        torch.cat(words, out=out[2 * (B + 1):2 * (3 * B + 2)].view(torch.int32))
+        return out
+
     def _to_host(self, t):
         """One device-to-host copy of t through a reused pinned buffer, and
         the host sync that completes it."""
@@ -395,12 +498,15 @@ class EmoVITS(object):
         torch.cuda.current_stream(self.device).synchronize()
         return buf[:n].numpy().copy()
 
-    def _infer_graph_batch(self, texts, emos, spkids, duration_rate, post=None):
+    def _infer_graph_batch(self, texts, emos, spkids, duration_rate, post=None, rates=None):
         """2..16 utterances as one replay of a batched utterance graph, cached
         with the B = 1 graphs per (batch bucket, text bucket, frame bucket,
-        rate).  The noise starts are drawn on the device in row order from
-        ONE pool of raw words of numpy's generator (ops.draw_starts), so they
-        and the generator's final state are those of consecutive infer calls.
+        rate); with ``rates`` (one speed per row; ``duration_rate`` unused)
+        a rate-free graph whose speeds are a device input, cached per
+        ("rows", batch bucket, text bucket, frame bucket) for every speed.
+        The noise starts are drawn on the device in row order from ONE pool
+        of raw words of numpy's generator (ops.draw_starts), so they and the
+        generator's final state are those of consecutive infer calls.
         Returns (wav [B, 1, frames * hop] on the device, y_len list), or with
         ``post(wav [B, frames * hop], y_len, n_rows, (y_len, status,
         used_total))`` -> the int16 buffer of _post_pack: ((pcm, offsets),
@@ -418,29 +524,33 @@ class EmoVITS(object):
         emo = torch.cat(emos)
         sid = torch.tensor(spkids, dtype=torch.long)
         pool_mult = 1
+        memo = (bb, xb, duration_rate) if rates is None else ("rows", bb, xb)
         while True:
-            tyb = self._ty_bucket.get((bb, xb, duration_rate), 256)
-            key = (bb, xb, tyb, float(duration_rate))
+            tyb = self._ty_bucket.get(memo, 256)
+            key = (bb, xb, tyb, float(duration_rate)) if rates is None else ("rows", bb, xb, tyb)
             run = self._graphs.pop(key, None)
             if run is None:
                 while len(self._graphs) >= self.max_graphs:
                     self._graphs.pop(next(iter(self._graphs)))
                 run = self.model.capture_infer_bucketed(
-                    xb, tyb, noise_len=self.noise.numel(), padded_text=True,
-                    length_scale=duration_rate, batch=bb)
+                    xb, tyb, noise_len=self.noise.numel(), padded_text=True, batch=bb,
+                    length_scale=duration_rate if rates is None else torch.ones(bb))
                 run.static["noise"].copy_(self.noise.float())
             self._graphs[key] = run  # most recently used last
             pool, state = ops.numpy_draw_pool(run.pool_len * pool_mult)
             if pool_mult == 1:
-                wav, y_len, status, used = run(x, emo, sid, lengths, pool, n)
+                if rates is None:
+                    wav, y_len, status, used = run(x, emo, sid, lengths, pool, n)
+                else:
+                    wav, y_len, status, used = run(x, emo, sid, lengths, pool, n, rates=rates)
             else:
                 # the graph's pool is static: the (p < 2^-32 per row) longer
                 # pool runs the same kernels eagerly on the graph's inputs
                 st = run.static
                 wav, y_len, status, used = self.model.infer_bucketed(
                     st["x"], st["emo"], st["sid"], st["noise"], tyb, x_lengths=st["xl"],
-                    length_scale=duration_rate, noise_start=torch.from_numpy(pool).to(self.device),
-                    n_rows=st["n_rows"])
+                    length_scale=duration_rate if rates is None else st["rates"],
+                    noise_start=torch.from_numpy(pool).to(self.device), n_rows=st["n_rows"])
             words = (y_len, status, used)
             if post is None:
                 host = torch.cat(words).tolist()  # (synchronises)
@@ -456,7 +566,7 @@ class EmoVITS(object):
                 if tyb >= 4096:
                     raise RuntimeError(f"utterance of {max(y)} frames exceeds the 4096-frame "
                                        "noise buffer")
-                self._ty_bucket[(bb, xb, duration_rate)] = min(4096, 1 << (max(y) - 1).bit_length())
+                self._ty_bucket[memo] = min(4096, 1 << (max(y) - 1).bit_length())
                 continue
             if -2 in st_rows:
                 np.random.set_state(state)

@@ -522,8 +522,14 @@ class SynthesizerTrn(nn.Module):
         of a batch bucket and draw nothing).  ops.draw_starts draws every
         row's start in row order from the one pool, the expansion reads them
         (vits_expand_durations mode 2).  Returns (wav, y_len [B], status
-        [B], used_total [1]) as ops.draw_starts defines them."""
+        [B], used_total [1]) as ops.draw_starts defines them.
+
+        ``length_scale``: a number, or a contiguous fp32 [B] device tensor
+        of per-row speeds read on the device (ops.expand_durations'
+        ``rate``): row b is then what the call with float(length_scale[b])
+        computes, and a captured graph serves every mix of speeds."""
         engine._check_gpu(x, "SynthesizerTrn.infer_bucketed")
+        rate = length_scale if isinstance(length_scale, torch.Tensor) else float(length_scale)
         dt = x.dtype
         shared_pool = noise_start is not None and noise_start.dim() == 1
         if shared_pool and n_rows is None:
@@ -541,11 +547,11 @@ class SynthesizerTrn(nn.Module):
         starts = None
         if shared_pool:
             starts, y_len, status, used_total = engine.ops.draw_starts(
-                logw, m_p.shape[1], noise.numel(), noise_start, rate=float(length_scale),
+                logw, m_p.shape[1], noise.numel(), noise_start, rate=rate,
                 x_len=xl, half_round=dt == torch.float16, n_rows=n_rows)
             noise_start = None
         z, lens = engine.ops.expand_durations(
-            logw, m_p, s_p, noise, int(t_y), rate=float(length_scale), x_len=xl,
+            logw, m_p, s_p, noise, int(t_y), rate=rate, x_len=xl,
             noise_start=noise_start, half_round=dt == torch.float16,
             stage_mult=self._stage_mult(), starts=starts)
         gf = engine._f32(g)
@@ -577,7 +583,13 @@ class SynthesizerTrn(nn.Module):
         [pool_len], n_rows=n) -> (wav [batch, 1, t_y * hop], y_len [batch],
         status [batch], used_total [1]), views of static buffers.  Text rows
         are zeroed past their length; rows at or past n are padding: zero
-        text, length 0 (y_len 1), no draw."""
+        text, length 0 (y_len 1), no draw.
+
+        ``length_scale`` as an fp32 [batch] tensor (its values: the initial
+        speeds) captures a rate-free graph: the speeds live in the static
+        buffer ``rates`` and replay takes them per call, batch > 1 as
+        run(..., rates=[n floats]) (padding rows get 1.0), batch 1 as
+        run(..., rate=float); without them the buffer keeps what it holds."""
         if batch > 1:
             return self._capture_infer_batch(t_x, t_y, int(batch), noise_len, padded_text,
                                              length_scale, warmup, pool_len)
@@ -590,12 +602,14 @@ class SynthesizerTrn(nn.Module):
                       start=torch.zeros(1, engine.ops.ED_DRAWS, device=dev, dtype=torch.int32),
                       xl=torch.full((1,), t_x, device=dev, dtype=torch.int32),
                       noise=torch.zeros(noise_len if noise_len else C * t_y, device=dev))
+        if isinstance(length_scale, torch.Tensor):
+            static["rates"] = length_scale.to(device=dev, dtype=torch.float32).reshape(1).clone()
 
         def body():
             noise = static["noise"] if noise_len else static["noise"].view(1, C, t_y)
             return self.infer_bucketed(static["x"], static["emo"], static["sid"], noise, t_y,
                                        x_lengths=static["xl"] if padded_text else None,
-                                       length_scale=length_scale,
+                                       length_scale=static.get("rates", length_scale),
                                        noise_start=static["start"] if noise_len else None)
 
         s = torch.cuda.Stream(device=dev)
@@ -608,7 +622,11 @@ class SynthesizerTrn(nn.Module):
         with torch.cuda.graph(graph):
             out = body()
 
-        def run(x, emo, sid, noise=None, noise_start=None, x_length=None):
+        def run(x, emo, sid, noise=None, noise_start=None, x_length=None, rate=None):
+            if rate is not None:
+                if "rates" not in static:
+                    raise ValueError("replay: this graph was captured at a fixed length_scale")
+                static["rates"].fill_(float(rate))
             if padded_text:
                 n = x.shape[1] if x_length is None else int(x_length)
                 static["x"].zero_()
@@ -645,11 +663,15 @@ class SynthesizerTrn(nn.Module):
                       pool=torch.zeros(P, device=dev, dtype=torch.int32),
                       n_rows=torch.zeros(1, device=dev, dtype=torch.int32),
                       noise=torch.zeros(noise_len, device=dev))
+        if isinstance(length_scale, torch.Tensor):
+            static["rates"] = length_scale.to(device=dev, dtype=torch.float32).reshape(
+                batch).clone()
         cols = torch.arange(t_x, device=dev).view(1, t_x, 1)
 
         def body():
             return self.infer_bucketed(static["x"], static["emo"], static["sid"], static["noise"],
-                                       t_y, x_lengths=static["xl"], length_scale=length_scale,
+                                       t_y, x_lengths=static["xl"],
+                                       length_scale=static.get("rates", length_scale),
                                        noise_start=static["pool"], n_rows=static["n_rows"])
 
         s = torch.cuda.Stream(device=dev)
@@ -662,8 +684,17 @@ class SynthesizerTrn(nn.Module):
         with torch.cuda.graph(graph):
             out = body()
 
-        def run(x, emo, sid, x_lengths, pool, n_rows=None):
+        def run(x, emo, sid, x_lengths, pool, n_rows=None, rates=None):
             n = x.shape[0] if n_rows is None else int(n_rows)
+            if rates is not None:
+                if "rates" not in static:
+                    raise ValueError("batched replay: this graph was captured at a fixed "
+                                     "length_scale")
+                rates = [float(v) for v in rates][:n]
+                if len(rates) != n:
+                    raise ValueError(f"batched replay: {n} rows need {n} rates, got {len(rates)}")
+                static["rates"].copy_(torch.tensor(rates + [1.0] * (batch - n),
+                                                   dtype=torch.float32))
             lengths = [int(v) for v in x_lengths][:n]
             if not 1 <= n <= batch or len(lengths) != n or x.shape[1] > t_x or max(lengths) > x.shape[1]:
                 raise ValueError(f"batched replay: {n} rows of lengths {lengths} in x "

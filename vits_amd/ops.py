@@ -923,8 +923,27 @@ def numpy_draw_commit(state, used: int) -> None:
         np.random.randint(0, 2 ** 32, size=used, dtype=np.uint32)
 
 
+def _rate_arg(rate, B: int, what: str):
+    """``rate`` of expand_durations / draw_starts: a number (one speed for
+    every row, passed by value) or a contiguous fp32 [B] device tensor (row
+    b's speed, read on the device: the ``*_rows`` entry points).  Returns
+    (scalar, tensor): exactly one is not None."""
+    if isinstance(rate, torch.Tensor):
+        if rate.dtype != torch.float32 or tuple(rate.shape) != (B,) or not rate.is_contiguous():
+            raise _lib.VitsAmdError(
+                f"{what}: a per-row rate must be a contiguous fp32 [{B}] tensor, got "
+                f"{rate.dtype} {tuple(rate.shape)}")
+        require_device(rate)
+        return None, rate
+    numbers = (int, float, np.integer, np.floating)
+    if isinstance(rate, bool) or not isinstance(rate, numbers):
+        raise _lib.VitsAmdError(f"{what}: rate must be a number or an fp32 [{B}] device tensor, "
+                                f"got {type(rate).__name__}")
+    return float(rate), None
+
+
 def expand_durations(logw: torch.Tensor, m_p: torch.Tensor, s_p: torch.Tensor,
-                     noise: torch.Tensor, t_y: int, *, rate: float = 1.0,
+                     noise: torch.Tensor, t_y: int, *, rate=1.0,
                      noise_scale: float = 1.0, x_len: Optional[torch.Tensor] = None,
                      noise_start: Optional[torch.Tensor] = None, half_round: bool = False,
                      stage_mult=(1,), out: Optional[torch.Tensor] = None,
@@ -944,7 +963,10 @@ def expand_durations(logw: torch.Tensor, m_p: torch.Tensor, s_p: torch.Tensor,
     pool was rejected, the caller advances by the pool and calls again; z is
     zero for both).  ``starts`` (int64 [B], from ``draw_starts``) instead of
     ``noise_start``: the flat buffer read at those explicit starts (a
-    negative one: z = 0, nothing read); ``lens`` stays [n_stage, B]."""
+    negative one: z = 0, nothing read); ``lens`` stays [n_stage, B].
+    ``rate``: a number, or a contiguous fp32 [B] device tensor of per-row
+    speeds (row b is then bit for bit the call with ``rate=float(rate[b])``)."""
+    rate, rates = _rate_arg(rate, m_p.shape[0], "expand_durations")
     require_device(logw, m_p, s_p, noise)
     if starts is not None:
         if noise_start is not None:
@@ -977,13 +999,16 @@ def expand_durations(logw: torch.Tensor, m_p: torch.Tensor, s_p: torch.Tensor,
         raise _lib.VitsAmdError(f"expand_durations: noise_start must be int32 [{B}, {ED_DRAWS}]")
     else:
         mode, start_ptr = 1, noise_start.data_ptr()
-    check(_lib.load().vits_expand_durations(
-        logw.data_ptr(), logw.stride(0), _ptr(x_len), t_x, float(rate), int(half_round),
+    lib = _lib.load()
+    fn, what = ((lib.vits_expand_durations, "vits_expand_durations") if rates is None else
+                (lib.vits_expand_durations_rows, "vits_expand_durations_rows"))
+    check(fn(
+        logw.data_ptr(), logw.stride(0), _ptr(x_len), t_x,
+        rate if rates is None else rates.data_ptr(), int(half_round),
         m_p.data_ptr(), s_p.data_ptr(), m_p.stride(0), m_p.stride(1), noise.data_ptr(),
         mode, start_ptr, noise.numel(), float(noise_scale),
         out.data_ptr(),
-        B, C_, t_y, lens.data_ptr(), mult, n_stage, _stream_ptr(m_p.device)),
-        "vits_expand_durations")
+        B, C_, t_y, lens.data_ptr(), mult, n_stage, _stream_ptr(m_p.device)), what)
     return out, lens
 
 
@@ -1004,7 +1029,7 @@ def _n_rows_ptr(n_rows, B: int, device, what: str):
 
 
 def draw_starts(logw: torch.Tensor, channels: int, noise_len: int, pool: torch.Tensor, *,
-                rate: float = 1.0, x_len: Optional[torch.Tensor] = None,
+                rate=1.0, x_len: Optional[torch.Tensor] = None,
                 half_round: bool = False, n_rows=None, starts: Optional[torch.Tensor] = None,
                 meta: Optional[torch.Tensor] = None):
     """The noise-slice starts of B utterances as B consecutive EmoVITS.infer
@@ -1018,9 +1043,11 @@ def draw_starts(logw: torch.Tensor, channels: int, noise_len: int, pool: torch.T
     (nothing consumed), -2 = the pool ran out at this row; starts is -1 for
     both.  Rows at or past ``n_rows`` (None, int or int32 [1] device tensor)
     draw nothing.  When everything is >= 0, ``numpy_draw_commit(state,
-    used_total)`` leaves numpy's generator where the B calls would."""
-    require_device(logw, pool)
+    used_total)`` leaves numpy's generator where the B calls would.
+    ``rate``: a number or an fp32 [B] device tensor, as in expand_durations."""
     B = logw.shape[0]
+    rate, rates = _rate_arg(rate, B, "draw_starts")
+    require_device(logw, pool)
     logw = logw.reshape(B, -1).float().contiguous()
     t_x = logw.shape[1]
     if pool.dtype != torch.int32 or pool.dim() != 1 or not pool.is_contiguous() or not pool.numel():
@@ -1037,10 +1064,14 @@ def draw_starts(logw: torch.Tensor, channels: int, noise_len: int, pool: torch.T
                               or not x_len.is_contiguous()):
         raise _lib.VitsAmdError(f"draw_starts: x_len must be a contiguous int32 [{B}] tensor")
     keep, nr_ptr = _n_rows_ptr(n_rows, B, logw.device, "draw_starts")
-    check(_lib.load().vits_draw_starts(
-        logw.data_ptr(), logw.stride(0), _ptr(x_len), t_x, float(rate), int(half_round),
+    lib = _lib.load()
+    fn, what = ((lib.vits_draw_starts, "vits_draw_starts") if rates is None else
+                (lib.vits_draw_starts_rows, "vits_draw_starts_rows"))
+    check(fn(
+        logw.data_ptr(), logw.stride(0), _ptr(x_len), t_x,
+        rate if rates is None else rates.data_ptr(), int(half_round),
         int(channels), int(noise_len), pool.data_ptr(), pool.numel(), nr_ptr, B,
-        starts.data_ptr(), meta.data_ptr(), _stream_ptr(logw.device)), "vits_draw_starts")
+        starts.data_ptr(), meta.data_ptr(), _stream_ptr(logw.device)), what)
     return starts, meta[:B], meta[B:2 * B], meta[2 * B:]
 
 
@@ -1582,4 +1613,116 @@ def pack_pcm(rows: torch.Tensor, y_len: torch.Tensor, hop: int, passes=(), tail:
         rows.data_ptr(), rows.stride(0) if B > 1 else cap, cap, y_len.data_ptr(), int(hop), up,
         down, len(passes), tail, nr_ptr, B, offsets.data_ptr(), stream.data_ptr(),
         stream.numel(), _stream_ptr(rows.device)), "vits_pack_pcm")
+    return out, offsets, stream
+
+
+# -- per-row output stage: rows of different requests in one launch -------------
+
+
+def _row_ratios(what: str, ratios, B: int):
+    ratios = [_reduced(u, d) for u, d in ratios]
+    if len(ratios) != B:
+        raise _lib.VitsAmdError(f"{what}: one (up, down) per row: {B} rows, got {len(ratios)}")
+    return ratios
+
+
+def resample_rows(x: torch.Tensor, passes_per_row, *, lengths: torch.Tensor,
+                  length_scale: int = 1, volumes=None, pcm: bool = False,
+                  out: Optional[torch.Tensor] = None,
+                  out_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ONE resampling pass over x [B, cap] (fp32 / fp16 / bf16) in which row b
+    has its own ratio: ``passes_per_row`` holds one (up, down) per row, (1,
+    1) being the masked copy.  Row b is bit for bit resample_poly(x[b], up,
+    down) (``pcm=False``: fp32 out) or resample_pcm16 / pcm16 with
+    ``volumes[b]`` (``pcm=True``: int16 out; volumes None = 1.0).  The row
+    length is ``lengths[b] * length_scale`` (int32 [B] device tensor, read on
+    the device).  ``out`` is [B, out_cap] for one shared out_cap (default:
+    the largest resample_out_len(cap, up, down) of the rows); every row is
+    zero from its own n_out to out_cap and ``out_lengths`` (int32 [B])
+    receives n_out.  The filters are the cached tables of resample_filter
+    (the cache keeps them alive); the descriptors travel in the kernel
+    arguments, so the call makes no copy.  At most PACK_MAX_BATCH rows."""
+    what = "resample_rows"
+    require_device(x, lengths, out, out_lengths)
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise _lib.VitsAmdError(f"{what}: x must be fp32, fp16 or bf16, got {x.dtype}")
+    if x.dim() != 2 or x.stride(1) != 1 or x.shape[1] < 1:
+        raise _lib.VitsAmdError(f"{what}: x must be [B, n] with unit stride along n")
+    B, cap = x.shape
+    if B > PACK_MAX_BATCH:
+        raise _lib.VitsAmdError(f"{what}: at most {PACK_MAX_BATCH} rows, got {B}")
+    ratios = _row_ratios(what, passes_per_row, B)
+    if (not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32
+            or tuple(lengths.shape) != (B,) or not lengths.is_contiguous()):
+        raise _lib.VitsAmdError(f"{what}: lengths must be a contiguous int32 [{B}] device tensor")
+    volumes = [1.0] * B if volumes is None else [float(v) for v in volumes]
+    if len(volumes) != B:
+        raise _lib.VitsAmdError(f"{what}: one volume per row: {B} rows, got {len(volumes)}")
+    odt = torch.int16 if pcm else torch.float32
+    if out is None:
+        out_cap = max(resample_out_len(cap, u, d) for u, d in ratios)
+        out = torch.empty(B, max(1, out_cap), device=x.device, dtype=odt)
+    if (out.dtype != odt or out.dim() != 2 or out.shape[0] != B or out.stride(1) != 1
+            or out.shape[1] < 1):
+        raise _lib.VitsAmdError(f"{what}: out must be {odt} [{B}, out_cap] with unit stride")
+    if out_lengths is not None and (out_lengths.dtype != torch.int32
+                                    or tuple(out_lengths.shape) != (B,)
+                                    or not out_lengths.is_contiguous()):
+        raise _lib.VitsAmdError(f"{what}: out_lengths must be a contiguous int32 [{B}] tensor")
+    rows = (_lib.PostRow * B)()
+    for b, (up, down) in enumerate(ratios):
+        table, half_len = (None, 0) if up == down else resample_filter(up, down, x.device)
+        rows[b] = _lib.PostRow(_ptr(table), up, down, half_len,
+                               0 if table is None else table.shape[1], volumes[b], 0)
+    out_cap = out.shape[1]
+    check(_lib.load().vits_resample_poly_rows(
+        x.data_ptr(), _DT[x.dtype], x.stride(0) if B > 1 else cap, cap, lengths.data_ptr(),
+        int(length_scale), rows, None if pcm else out.data_ptr(), out.data_ptr() if pcm else None,
+        out.stride(0) if B > 1 else out_cap, out_cap, _ptr(out_lengths), B,
+        _stream_ptr(x.device)), "vits_resample_poly_rows")
+    return out
+
+
+def pack_pcm_rows(rows: torch.Tensor, y_len: torch.Tensor, hop: int, passes_per_row, tails, *,
+                  n_rows=None, out: Optional[torch.Tensor] = None,
+                  header: Optional[int] = None):
+    """pack_pcm for rows of different requests: ``passes_per_row[b]`` is row
+    b's list of at most two (up, down) passes and ``tails[b]`` its tail, so
+    n_out[b] and offsets[b + 1] = offsets[b] + n_out[b] + tails[b] follow the
+    row's own output stage.  Everything else (the layout of ``out``, n_rows,
+    no host sync) as pack_pcm; ``out`` defaults to header + B * (cap +
+    max(tails)) elements."""
+    what = "pack_pcm_rows"
+    require_device(rows, y_len, out)
+    if rows.dtype != torch.int16 or rows.dim() != 2 or rows.stride(1) != 1:
+        raise _lib.VitsAmdError(f"{what}: rows must be int16 [B, cap] with unit stride along cap")
+    B, cap = rows.shape
+    if B > PACK_MAX_BATCH:
+        raise _lib.VitsAmdError(f"{what}: at most {PACK_MAX_BATCH} rows, got {B}")
+    if y_len.dtype != torch.int32 or tuple(y_len.shape) != (B,) or not y_len.is_contiguous():
+        raise _lib.VitsAmdError(f"{what}: y_len must be a contiguous int32 [{B}] tensor")
+    passes_per_row, tails = list(passes_per_row), [int(t) for t in tails]
+    if len(passes_per_row) != B or len(tails) != B or min(tails) < 0:
+        raise _lib.VitsAmdError(f"{what}: one pass list and one tail >= 0 per row ({B} rows)")
+    up, down = (C.c_int32 * (2 * B))(), (C.c_int32 * (2 * B))()
+    for b, passes in enumerate(passes_per_row):
+        passes = [(u, d) for u, d in (_reduced(u, d) for u, d in passes) if u != d]
+        if len(passes) > 2:
+            raise _lib.VitsAmdError(f"{what}: at most two resampling passes per row")
+        for i in range(2):
+            up[2 * b + i], down[2 * b + i] = passes[i] if i < len(passes) else (1, 1)
+    header = pack_header_len(B) if header is None else int(header)
+    if header < pack_header_len(B) or header % 8:
+        raise _lib.VitsAmdError(f"{what}: header must be a multiple of 8, >= {pack_header_len(B)}")
+    if out is None:
+        out = torch.empty(header + B * (cap + max(tails)), device=rows.device, dtype=torch.int16)
+    if out.dtype != torch.int16 or out.dim() != 1 or not out.is_contiguous() or out.numel() <= header:
+        raise _lib.VitsAmdError(f"{what}: out must be a contiguous int16 [> header] tensor")
+    offsets = out[:2 * (B + 1)].view(torch.int32)
+    stream = out[header:]
+    keep, nr_ptr = _n_rows_ptr(n_rows, B, rows.device, what)
+    check(_lib.load().vits_pack_pcm_rows(
+        rows.data_ptr(), rows.stride(0) if B > 1 else cap, cap, y_len.data_ptr(), int(hop), up,
+        down, (C.c_int32 * B)(*tails), nr_ptr, B, offsets.data_ptr(), stream.data_ptr(),
+        stream.numel(), _stream_ptr(rows.device)), "vits_pack_pcm_rows")
     return out, offsets, stream

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .infer import EmoVITS
+from .infer import EmoVITS, PcmRequest
 
 
 def _gen_wav_header(sample_num, sample_rate=8000, bit_num=16):
@@ -63,6 +63,9 @@ class VITSWrap(object):
     # batch_segments batches a request of at least this many segments; fewer
     # run one after another (measured crossover: profiles/serve_batch_ab.txt)
     BATCH_MIN_SEGMENTS = 2
+    # speaking_many batches a call of at least this many segments in all;
+    # fewer run through speaking (measured crossover: profiles/serve_mixed_ab.txt)
+    MANY_MIN_ROWS = 2
 
     def __init__(self, ckpt_path: str = None, device: torch.device = None, loglv: int = 0, *,
                  textparser=None, speecher: EmoVITS = None, device_post: bool = False,
@@ -168,6 +171,12 @@ class VITSWrap(object):
                 segtexts.append(segtext)
                 seg_samples.append(len(wav))
                 t_back += time.time() - t1
+        return self._finish(inputs, texts, segtexts, seg_samples, batch_wav, batch_wavlen,
+                            sampling_rate, t_front, t_back)
+
+    def _finish(self, inputs, texts, segtexts, seg_samples, batch_wav, batch_wavlen, sampling_rate,
+                t_front, t_back):
+        """The result dict of ``speaking`` (vits_wrap.py:199-218)."""
         segment_info, start_ms, end_ms = [], 0.0, 0.0
         for text, segtext, n in zip(texts, segtexts, seg_samples):
             end_ms += n / sampling_rate * 1000
@@ -184,3 +193,45 @@ class VITSWrap(object):
         out["time_used_backend"] = t_back * 1000
         out["rtf"] = rtf
         return out
+
+    @torch.no_grad()
+    def speaking_many(self, list_of_inputs) -> list:
+        """``speaking`` for several requests at once: one dict per input, the
+        same ``wav``, ``sr`` and ``segment_info`` as ``[speaking(i) for i in
+        list_of_inputs]``.  With batch_segments=True and at least
+        MANY_MIN_ROWS segments in all, the front end runs over all segments
+        of all requests, then ONE EmoVITS.infer_pcm_requests call synthesises
+        them: requests with different speed, pitch, sampling rate, volume and
+        tail share graph replays of up to 16 rows, whatever their controls.
+        Every dict then reports the front-end and back-end times of the whole
+        call (the requests are not timed apart) and the call's rtf.  A request
+        without an explicit emotion id draws it before any noise draw of the
+        call (see infer_pcm_requests); with explicit emotions numpy's
+        generator ends where the loop leaves it.  Otherwise: the loop."""
+        list_of_inputs = list(list_of_inputs)
+        parsed = [self._parse_input(inputs) for inputs in list_of_inputs] \
+            if self.batch_segments else []
+        split = [self._split_utt_text(p[1], p[2]) for p in parsed]
+        if not self.batch_segments or sum(len(t) for _, t in split) < self.MANY_MIN_ROWS:
+            return [self.speaking(inputs) for inputs in list_of_inputs]
+        t0 = time.time()
+        front = [[self.textparser(uid, text) for uid, text in zip(ids, texts)]
+                 for ids, texts in split]
+        t1 = time.time()
+        requests = []
+        for p, segs in zip(parsed, front):
+            _, _, _, spkid, volume, speed, pitch, sampling_rate, tail_silence, emotion = p
+            _, emotion = self.speecher._resolve(spkid, emotion)
+            requests.append(PcmRequest([(spkid, vec, emotion) for _, _, vec in segs],
+                                       duration_rate=speed, pitch=pitch,
+                                       sampling_rate=sampling_rate, volume=volume,
+                                       tail_silence=tail_silence))
+        results = self.speecher.infer_pcm_requests(requests)
+        t_front, t_back = t1 - t0, time.time() - t1
+        total = sum(sum(n_model) for _, _, _, n_model in results)
+        outs = []
+        for p, (_, texts), segs, (pcm, offsets, _, _) in zip(parsed, split, front, results):
+            outs.append(self._finish(p[0], texts, [segtext for _, segtext, _ in segs],
+                                     [int(n) for n in np.diff(offsets)], [pcm], total, p[7],
+                                     t_front, t_back))
+        return outs
