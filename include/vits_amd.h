@@ -379,6 +379,39 @@ int vits_stft_mag_backward_multi(const vits_stft_job* jobs, int njobs, float* wo
                                  int64_t workspace_floats, void* stream);
 int64_t vits_stft_workspace_multi(const vits_stft_job* jobs, int njobs);
 
+/* Magnitude STFT of a ragged batch, each row's length read on the device  */
+/* (inference only: no re / im, layout [B][n_fft/2+1][frames_cap]), so the  */
+/* wave -> spectrogram step of voice conversion sits in a captured graph.   */
+/* x [B][cap] fp32 with row stride x_bstride; lens int32 [B] (device).      */
+/* Row b: L_b = clamp(lens[b], 0, cap); the reflect padding folds at the    */
+/* row's own end L_b - 1, and nothing at or past L_b is read.  frames_b =   */
+/* min((L_b + 2 pad - n_fft)/hop + 1, frames_cap) when L_b > pad and L_b +  */
+/* 2 pad >= n_fft, else 0; columns >= frames_b are written as 0;            */
+/* frames_out (int32 [B], optional) receives frames_b.  The first frames_b  */
+/* columns of row b are bit for bit vits_stft_mag_forward of that row alone */
+/* at length L_b.  VITS_E_ARG for a null x / mag / lens / window;           */
+/* VITS_E_SHAPE for frames_cap <= 0, x_bstride < cap, pad >= cap, win >     */
+/* n_fft, or a cap no frame fits (cap + 2 pad < n_fft).                     */
+int vits_stft_mag_forward_rows(const float* x, int64_t x_bstride, int batch, int cap,
+                               const int32_t* lens, const float* window, int n_fft, int hop,
+                               int win, int pad, float eps, float* mag, int frames_cap,
+                               int32_t* frames_out, void* stream);
+
+/* ---------------------------------------------------------------------- */
+/* Tail of the posterior encoder over a bucket (models.py:273-279 with the */
+/* mask of models.py:262-271): z[b][c][t] = m + (noise * s) * noise_scale   */
+/* for t < lens[b], 0 for lens[b] <= t < t_len.  m, s: the two outputs of   */
+/* the proj conv (s already through the ACT_EXP epilogue), rows of          */
+/* ms_cstride floats; noise [B][C][t_len] contiguous or NULL (z = m, the    */
+/* posterior mean); z [B][C][t_len] contiguous.  stage_lens (optional,      */
+/* int32 [n_stage][B]): stage_lens[i][b] = clamp(lens[b], 0, t_len) *       */
+/* stage_mult[i], the layout of vits_expand_durations' lens. n_stage <= 8.  */
+/* ---------------------------------------------------------------------- */
+int vits_posterior_sample(const float* m, const float* s, int64_t ms_bstride, int32_t ms_cstride,
+                          const float* noise, float noise_scale, const int32_t* lens, float* z,
+                          int batch, int channels, int t_len, int32_t* stage_lens,
+                          const int32_t* stage_mult, int n_stage, void* stream);
+
 /* ---------------------------------------------------------------------- */
 /* channel LayerNorm over dim 1 of [B][C][T]:                             */
 /*   v = LN(x + r) * gamma + beta                (r, gamma, beta optional) */

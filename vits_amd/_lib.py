@@ -470,6 +470,16 @@ _SIGS = {
         [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     ),
+    "vits_stft_mag_forward_rows": (
+        C.c_int,
+        [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+         C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    ),
+    "vits_posterior_sample": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,
+         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    ),
     "vits_amd_version": (C.c_char_p, []),
     "vits_amd_device_arch": (C.c_int, [C.c_char_p, C.c_int]),
     "vits_dispatch_count": (C.c_int64, [C.c_int]),

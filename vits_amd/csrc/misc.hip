@@ -493,7 +493,55 @@ __global__ __launch_bounds__(256) void conv_post_tanh_v4_kernel(const XT* __rest
   y[(int64_t)b * t_len + t] = tanhf(acc);
 }
 
+// ---------------------------------------------------------------------------
+// Posterior sample over a bucket: z = m + (noise * s) * noise_scale (the
+// arithmetic of expand_durations_kernel's step 3) for t < lens[b], 0 past it;
+// noise == nullptr: z = m.  Workgroup = (256 frames, channel, utterance);
+// the first workgroup of a row also writes its per-stage lengths.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void posterior_sample_kernel(
+    const float* __restrict__ m, const float* __restrict__ s, int64_t ms_bstride, int ms_cstride,
+    const float* __restrict__ noise, float noise_scale, const int32_t* __restrict__ lens,
+    float* __restrict__ z, int channels, int t_len, int batch, int32_t* __restrict__ stage_lens,
+    const EdStages st) {
+  const int b = blockIdx.z, c = blockIdx.y;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int len = min(max(lens[b], 0), t_len);
+  if (stage_lens && blockIdx.x == 0 && c == 0 && threadIdx.x < st.n)
+    stage_lens[threadIdx.x * batch + b] = len * st.mult[threadIdx.x];
+  if (t >= t_len) return;
+  const int64_t o = ((int64_t)b * channels + c) * t_len + t;
+  float v = 0.f;
+  if (t < len) {
+    const int64_t i = (int64_t)b * ms_bstride + (int64_t)c * ms_cstride + t;
+    v = m[i];
+    if (noise) v = v + (noise[o] * s[i]) * noise_scale;
+  }
+  z[o] = v;
+}
+
 }  // namespace
+
+extern "C" int vits_posterior_sample(const float* m, const float* s, int64_t ms_bstride,
+                                     int32_t ms_cstride, const float* noise, float noise_scale,
+                                     const int32_t* lens, float* z, int batch, int channels,
+                                     int t_len, int32_t* stage_lens, const int32_t* stage_mult,
+                                     int n_stage, void* stream) {
+  VITS_CHECK_ARG(m && s && lens && z);
+  VITS_CHECK_SHAPE(batch > 0 && batch <= 65535 && channels > 0 && channels <= 65535 &&
+                   t_len > 0 && ms_cstride >= t_len);
+  EdStages st{};
+  if (stage_lens) {
+    VITS_CHECK_ARG(n_stage >= 1 && n_stage <= ED_MAX_STAGES && (n_stage == 1 || stage_mult));
+    st.n = n_stage;
+    for (int i = 0; i < n_stage; ++i) st.mult[i] = stage_mult ? stage_mult[i] : 1;
+  }
+  dim3 grid((t_len + 255) / 256, channels, batch);
+  hipLaunchKernelGGL(posterior_sample_kernel, grid, dim3(256), 0, as_stream(stream), m, s,
+                     ms_bstride, ms_cstride, noise, noise_scale, lens, z, channels, t_len, batch,
+                     stage_lens, st);
+  return vits_launch_status();
+}
 
 extern "C" int vits_linear_forward(const float* g, int64_t g_bstride, const float* w,
                                    const float* bias, float* y, int64_t y_bstride, int batch,

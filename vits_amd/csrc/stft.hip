@@ -207,6 +207,8 @@ struct StftJobD {
   int L, n, log2n, hop, win, pad, frames, fpb, batch;
   float eps;
   int fmajor;  // mag / re / im / grad_mag as [B][frames][n/2+1] (else [B][n/2+1][frames])
+  int fstride;  // forward, bin-major layout: floats from one bin to the next (frames;
+                // frames_cap for the ragged rows, whose frame counts differ per row)
 };
 
 // forward: frames f0 .. f0+fpb-1 of utterance b (radix-4 Stockham, fft_lds4;
@@ -263,7 +265,7 @@ __device__ void stft_fwd_block(const StftJobD& J, int fblk, int b, float2* sfft)
     const int fr = f0 + f;
     if (fr >= J.frames) continue;
     const float2 c = out[f * n + k];
-    const int64_t o = ((int64_t)b * nb + k) * J.frames + fr;
+    const int64_t o = ((int64_t)b * nb + k) * J.fstride + fr;
     J.mag[o] = sqrtf(c.x * c.x + c.y * c.y + J.eps);
     if (J.re) J.re[o] = c.x;
     if (J.im) J.im[o] = c.y;
@@ -576,7 +578,7 @@ __device__ void stft_fwd2_block(const StftJobD& J, int fblk, int b, float* sm) {
         const int k = k1 + N1 * (2 * q + par);
         if (k < nb) {
           const int64_t o = J.fmajor ? ((int64_t)b * J.frames + fr) * nb + k
-                                     : ((int64_t)b * nb + k) * J.frames + fr;
+                                     : ((int64_t)b * nb + k) * J.fstride + fr;
           J.mag[o] = sqrtf(xr[q] * xr[q] + xi[q] * xi[q] + J.eps);
           if (J.re) J.re[o] = xr[q];
           if (J.im) J.im[o] = xi[q];
@@ -608,7 +610,7 @@ __device__ void stft_fwd2_block(const StftJobD& J, int fblk, int b, float* sm) {
       const int k = k1 + N1 * k2;
       if (k < nb) {
         const int64_t o = J.fmajor ? ((int64_t)b * J.frames + fr) * nb + k
-                                   : ((int64_t)b * nb + k) * J.frames + fr;
+                                   : ((int64_t)b * nb + k) * J.fstride + fr;
         J.mag[o] = sqrtf(xr[k2] * xr[k2] + xi[k2] * xi[k2] + J.eps);
         if (J.re) J.re[o] = xr[k2];
         if (J.im) J.im[o] = xi[k2];
@@ -683,6 +685,69 @@ __global__ __launch_bounds__(256) void stft_fwd2_multi_kernel(const StftJobs J) 
   stft_fwd2_any(J.job[j], local - b * J.per_b[j], b, sm2);
 }
 
+// ---- ragged rows: row b's length is read from lens[b] on the device.  The
+// job arrives with L = the buffer's cap and fstride = frames_cap; each
+// workgroup narrows its copy to its row (x, mag, L, frames) and runs the very
+// block function of the fixed-length kernels as "utterance 0" - the same
+// frame grouping and arithmetic, hence the same bits as that row transformed
+// alone.  reflect_idx needs pad < L: a row with L_b <= pad has no frames and
+// runs no transform.  Columns at or past frames_b are zeroed by the workgroup
+// that owns them; nothing at or past L_b is read (every load goes through
+// reflect_idx(., L_b) or the live-frame predicate).
+struct StftRows {
+  const int32_t* lens;   // [B]
+  int32_t* frames_out;   // [B] or null
+  int64_t xstride;       // floats between rows of x
+  int cap;               // samples a row can hold
+  int frames_cap;        // columns of mag per bin
+};
+
+// narrows J to row b; returns frames_b
+__device__ __forceinline__ int stft_row_job(StftJobD& J, const StftRows& R, int b) {
+  const int L = min(max(R.lens[b], 0), R.cap);
+  int frames = 0;
+  if (L > J.pad && L + 2 * J.pad >= J.n)
+    frames = min((L + 2 * J.pad - J.n) / J.hop + 1, R.frames_cap);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && R.frames_out) R.frames_out[b] = frames;
+  J.x += (int64_t)b * R.xstride;
+  J.mag += (int64_t)b * (J.n / 2 + 1) * R.frames_cap;
+  J.L = L;
+  J.frames = frames;
+  return frames;
+}
+
+// zero columns [max(f0, frames), min(f0 + span, frames_cap)) of every bin
+__device__ __forceinline__ void stft_row_zero(const StftJobD& J, const StftRows& R, int f0,
+                                              int span, int frames) {
+  const int z0 = max(f0, frames);
+  const int nz = min(f0 + span, R.frames_cap) - z0;
+  if (nz <= 0) return;
+  const int nb = J.n / 2 + 1;
+  for (int i = threadIdx.x; i < nb * nz; i += blockDim.x) {
+    const int k = i / nz;
+    J.mag[(int64_t)k * R.frames_cap + z0 + (i - k * nz)] = 0.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void stft_fwd_rows_kernel(const StftJobD J0, const StftRows R) {
+  extern __shared__ float2 sfft[];
+  StftJobD J = J0;
+  const int frames = stft_row_job(J, R, blockIdx.y);
+  const int f0 = blockIdx.x * J.fpb;
+  if (f0 < frames) stft_fwd_block(J, blockIdx.x, 0, sfft);  // (workgroup-uniform)
+  stft_row_zero(J, R, f0, J.fpb, frames);
+}
+
+__global__ __launch_bounds__(256) void stft_fwd2_rows_kernel(const StftJobD J0, const StftRows R) {
+  extern __shared__ float sm2[];
+  StftJobD J = J0;
+  const int frames = stft_row_job(J, R, blockIdx.y);
+  const int F = fwd2_frames(J.n);
+  const int f0 = blockIdx.x * F;
+  if (f0 < frames) stft_fwd2_any(J, blockIdx.x, 0, sm2);  // (workgroup-uniform)
+  stft_row_zero(J, R, f0, F, frames);
+}
+
 __global__ __launch_bounds__(256) void stft_bwd_frames_kernel(const StftJobD J) {
   extern __shared__ float2 sfft[];
   stft_bwd_frames_block(J, blockIdx.x, blockIdx.y, sfft);
@@ -733,6 +798,7 @@ int make_job(StftJobD& J, const float* x, int batch, int length, const float* wi
   J.win = win;
   J.pad = pad;
   J.frames = frames;
+  J.fstride = frames;
   J.fpb = n_fft >= 1024 ? 1 : 1024 / n_fft;
   J.batch = batch;
   J.eps = eps;
@@ -778,6 +844,35 @@ extern "C" int vits_stft_mag_forward(const float* x, int batch, int length, cons
   }
   dim3 grid(job_fblocks(J), batch);
   hipLaunchKernelGGL(stft_fwd_kernel, grid, dim3(256), job_lds(J), as_stream(stream), J);
+  return vits_launch_status();
+}
+
+extern "C" int vits_stft_mag_forward_rows(const float* x, int64_t x_bstride, int batch, int cap,
+                                          const int32_t* lens, const float* window, int n_fft,
+                                          int hop, int win, int pad, float eps, float* mag,
+                                          int frames_cap, int32_t* frames_out, void* stream) {
+  VITS_CHECK_ARG(x && mag && lens);
+  VITS_CHECK_SHAPE(frames_cap > 0 && x_bstride >= cap);
+  StftJobD J;
+  // (the job of the whole buffer: refuses pad >= cap, win > n_fft and a cap no frame fits)
+  int rc = make_job(J, x, batch, cap, window, n_fft, hop, win, pad, eps);
+  if (rc) return rc;
+  J.mag = mag;
+  J.fstride = frames_cap;
+  StftRows R;
+  R.lens = lens;
+  R.frames_out = frames_out;
+  R.xstride = x_bstride;
+  R.cap = cap;
+  R.frames_cap = frames_cap;
+  if (use_fwd2(n_fft, hop)) {
+    const int F = fwd2_frames(n_fft);
+    hipLaunchKernelGGL(stft_fwd2_rows_kernel, dim3((frames_cap + F - 1) / F, batch), dim3(256),
+                       fwd2_lds(n_fft, hop), as_stream(stream), J, R);
+    return vits_launch_status();
+  }
+  hipLaunchKernelGGL(stft_fwd_rows_kernel, dim3((frames_cap + J.fpb - 1) / J.fpb, batch), dim3(256),
+                     job_lds(J), as_stream(stream), J, R);
   return vits_launch_status();
 }
 

@@ -12,7 +12,8 @@ Reference semantics followed per plan (paths in emotional-vits/):
   GeneratorPlan      models.py:306-318 + modules.py:250-260
   CouplingFlowPlan   models.py:228-235 (flows_reversed) + modules.py:362-375
                      + modules.py:157-182 (WN.infer); also the masked
-                     reverse flow of models.py:219-226 / modules.py:341-360
+                     reverse flow of models.py:219-226 / modules.py:341-360 and
+                     the forward flow of models.py:219-222 (voice conversion)
   TextEncoderPlan    models.py:167-189 + attentions.py:12-54,57-100,129-166
   DurationPlan       models.py:49-67
   PosteriorPlan      models.py:264-279 + modules.py:130-182
@@ -412,8 +413,15 @@ class CouplingFlowPlan:
         return ops.linear_rows(g, self.cond_w, self.cond_b)
 
     def run_(self, z: torch.Tensor, g: torch.Tensor, cond: Optional[torch.Tensor] = None,
-             lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Reverse flow in place on z [B, 2*half, T] (fp32 contiguous)."""
+             lengths: Optional[torch.Tensor] = None, forward: bool = False) -> torch.Tensor:
+        """Reverse flow in place on z [B, 2*half, T] (fp32 contiguous).
+        ``forward``: the forward flow instead, as ResidualCouplingBlock.forward
+        (models.py:219-222) runs it with a mask of ones (or of ``lengths``):
+        the same packed couplings in the opposite order, each adding its mean
+        (x1 <- x1 + m(x0; g), modules.py:352-354 mean-only).  The number of
+        Flips is even, so a coupling has the same parity of Flips in front of
+        it in either direction: every layer keeps the channel halves and the
+        folded weights it has in the reverse flow."""
         B, _, T = z.shape
         if cond is None:
             cond = self.conds(g)
@@ -423,14 +431,15 @@ class CouplingFlowPlan:
         skip = torch.empty_like(h)
         abuf = torch.empty_like(h)
         descs = []
-        for L in self.layers:
+        for L in (reversed(self.layers) if forward else self.layers):
             half = L["half"]
             src_off, dst_off = (half, 0) if L["flipped"] else (0, half)
             descs.append(make_desc(L["pre"], z, make_out(h), x_channel_offset=src_off,
                                    lengths=lengths))
             descs += L["wn"].descs(h, skip, abuf, cond, lengths)
             descs.append(make_desc(L["post"], skip, make_out(
-                z, res=z, res_scale=-1.0, channel_offset=dst_off), lengths=lengths))
+                z, res=z, res_scale=1.0 if forward else -1.0, channel_offset=dst_off),
+                lengths=lengths))
         ops.conv1d_launch_seq(descs, B, dev)
         return z
 
@@ -627,6 +636,34 @@ class PosteriorPlan:
         z.copy_(m).addcmul_(_f32(noise), s)
         return z
 
+    def run_bucketed(self, spec: torch.Tensor, noise: Optional[torch.Tensor], lens: torch.Tensor,
+                     noise_scale: float = 1.0, stage_mult=None):
+        """The posterior sample over a bucket, kernels only (no torch op, no
+        host sync): spec [B, F, T] fp32, ``lens`` int32 [B] on the device.
+        Every layer is masked at lens (PosteriorEncoder.forward's x_mask,
+        models.py:262-271), so row b is what ``run`` gives on its first
+        lens[b] frames and 0 past them; tiles past lens + the active
+        ops.length_skip margin are skipped.  z = m + noise * exp(logs) *
+        noise_scale (noise None: z = m).  With ``stage_mult`` returns (z,
+        stage lengths int32 [n, B]) as ops.posterior_sample does."""
+        B, _, T = spec.shape
+        dev = spec.device
+        assert self.cond_w is None, "the posterior encoder of the inference path is speaker-free"
+        h0 = torch.empty(B, self.H, T, device=dev, dtype=torch.float32)
+        ops.conv1d_launch(make_desc(self.pre, spec, make_out(h0), lengths=lens), B, dev)
+        g1, b1, e1 = self.ln
+        h = torch.empty_like(h0)
+        ops.layer_norm_channels(h0, g1, b1, e1, out=h, lengths=lens)
+        skip = torch.empty_like(h)
+        ops.conv1d_launch_seq(self.wn.descs(h, skip, h0, None, lens), B, dev)
+        Cc = self.out_channels
+        ms = torch.empty(B, 2 * Cc, T, device=dev, dtype=torch.float32)
+        ops.conv1d_launch(make_desc(self.proj, skip, make_out(ms),
+                                    out1=make_out(ms, act=ACT_EXP, channel_offset=Cc),
+                                    split=Cc, lengths=lens), B, dev)
+        return ops.posterior_sample(ms[:, :Cc], ms[:, Cc:], noise, lens,
+                                    noise_scale=noise_scale, stage_mult=stage_mult)
+
 
 # ---------------------------------------------------------------------------
 # module-level entry points used by modules.py / attentions.py / models.py
@@ -645,11 +682,12 @@ def generator_forward(gen, x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     return out.to(x.dtype)
 
 
-def flow_infer(block, x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+def flow_infer(block, x: torch.Tensor, g: torch.Tensor, reverse: bool = True) -> torch.Tensor:
+    """reverse=False: the forward flow (CouplingFlowPlan.run_ forward=True)."""
     _check_gpu(x, "ResidualCouplingBlock.infer")
     plan = get_plan(block, CouplingFlowPlan)
     z = _f32(x).clone()
-    plan.run_(z, _f32(g))
+    plan.run_(z, _f32(g), forward=not reverse)
     return z.to(x.dtype)
 
 

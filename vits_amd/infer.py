@@ -54,6 +54,7 @@ class EmoVITS(object):
         self._graphs = {}
         self._ty_bucket = {}
         self._pinned = {}
+        self._vc_gen = None  # device generator of convert's posterior draws (made on first use)
         if checkpoint_path is None and model is None:
             checkpoint_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "checkpoint",
                                            "checkpoint.pth")
@@ -582,6 +583,202 @@ class EmoVITS(object):
             offs = buf[:2 * (bb + 1)].view(np.int32)[:n + 1]
             return (buf[header:header + int(offs[n])], offs), y
 
+    # -- voice conversion: waveform in, waveform out --------------------------------
+    # frame buckets of the conversion graphs: powers of two, 256 .. 4096
+    VC_MIN_FRAMES, VC_MAX_FRAMES = 256, 4096
+
+    def _vc_stft(self):
+        """(filter_length, hop_length, win_length) of the data config."""
+        d = self.hps.data
+        missing = [k for k in ("filter_length", "hop_length", "win_length") if k not in d]
+        if missing:
+            raise ValueError(f"voice conversion needs data.{', data.'.join(missing)} in the config")
+        return int(d["filter_length"]), int(d["hop_length"]), int(d["win_length"])
+
+    def _map_spkid(self, spkid):
+        spkid = self.spkid_mapping.get(spkid, spkid)  # (the mapping of _resolve)
+        assert spkid < self.num_speaker, f"spkid={spkid} must be less than {self.num_speaker}"
+        return int(spkid)
+
+    @classmethod
+    def _vc_bucket(cls, frames):
+        """The smallest frame bucket (a power of two, 256 .. 4096) holding ``frames``."""
+        if frames > cls.VC_MAX_FRAMES:
+            raise ValueError(f"recording of {frames} frames exceeds the largest conversion bucket "
+                             f"of {cls.VC_MAX_FRAMES} frames (chunk it)")
+        return max(cls.VC_MIN_FRAMES, 1 << max(0, int(frames) - 1).bit_length())
+
+    def _vc_plan(self, n_in, sampling_rate_in=None):
+        """Host arithmetic of one recording of n_in samples at sampling_rate_in
+        (None: the model's rate): ((up, down) of the input resampling or None,
+        samples at the model rate, frames, frame bucket).  Raises ValueError
+        for a recording of at most pad = (n_fft - hop) / 2 samples (the
+        reflect padding needs more) or of more than 4096 frames."""
+        n_fft, hop, _ = self._vc_stft()
+        ratio, n = None, int(n_in)
+        if sampling_rate_in is not None and int(sampling_rate_in) != self.sampling_rate:
+            ratio = ops.resample_ratio(int(sampling_rate_in), self.sampling_rate)
+            n = ops.resample_out_len(n, *ratio)
+        pad = (n_fft - hop) // 2
+        if n <= pad:
+            raise ValueError(f"recording of {n} samples at {self.sampling_rate} Hz is too short: "
+                             f"voice conversion needs more than {pad}")
+        frames = n // hop
+        return ratio, n, frames, self._vc_bucket(frames)
+
+    def _vc_input(self, wav, sampling_rate_in):
+        """One recording on the device at the model rate: (fp32 [n], frames,
+        bucket).  int16 is scaled by 1 / 32768 (data_utils), floats are taken
+        as they are; another rate takes one ops.resample_poly pass (the host
+        knows every length: no sync)."""
+        wav = np.asarray(wav).reshape(-1)
+        ratio, n, frames, bucket = self._vc_plan(wav.shape[0], sampling_rate_in)
+        if wav.dtype == np.int16:
+            x = torch.from_numpy(wav.astype(np.float32) / 32768.0)
+        elif np.issubdtype(wav.dtype, np.floating):
+            x = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+        else:
+            raise ValueError(f"wav must be int16 or float, got {wav.dtype}")
+        x = x.to(self.device)
+        if ratio is not None:
+            x = ops.resample_poly(x, *ratio)
+            assert x.numel() >= n
+            x = x[:n]
+        return x, frames, bucket
+
+    def _convert_rows(self, wavs, srcs, tgts, sampling_rate_in, noise_scale, post=None):
+        """1 .. MAX_BATCH recordings through one conversion graph, cached in
+        self._graphs under ("vc", batch bucket, frame bucket) (graph=False:
+        the same convert_bucketed call, eagerly).  Returns (wav_out [B, 1,
+        bucket * hop] fp32 on the device, frames list), or with ``post(wav
+        [B, bucket * hop], y_len int32 [B])`` its result in place of the
+        waveform.  No host sync: the host knows every length."""
+        if self.device.type != "cuda":
+            raise ops._lib.VitsAmdError("EmoVITS.convert: the vits_amd inference path runs on a "
+                                        f"ROCm GPU only (got {self.device})")
+        stft = self._vc_stft()
+        hop = stft[1]
+        rows = [self._vc_input(w, sampling_rate_in) for w in wavs]
+        frames = [f for _, f, _ in rows]
+        tyb = max(b for _, _, b in rows)
+        n = len(rows)
+        bb = 1 if n == 1 else self._batch_bucket(n)
+        src = [self._map_spkid(s) for s in srcs]
+        tgt = [self._map_spkid(s) for s in tgts]
+        lens = [x.numel() for x, _, _ in rows]
+        x = torch.zeros(n, max(lens), device=self.device)
+        for i, (r, _, _) in enumerate(rows):
+            x[i, :lens[i]] = r
+        noise = None
+        if noise_scale > 0:
+            if self._vc_gen is None:
+                self._vc_gen = torch.Generator(device=self.device)
+            noise = torch.randn(n, self.inter_channels, tyb, device=self.device,
+                                generator=self._vc_gen) * float(noise_scale)
+        if self.graph:
+            key = ("vc", bb, tyb)
+            run = self._graphs.pop(key, None)
+            if run is None:
+                while len(self._graphs) >= self.max_graphs:
+                    self._graphs.pop(next(iter(self._graphs)))
+                run = self.model.capture_convert_bucketed(tyb, batch=bb, stft=stft)
+            self._graphs[key] = run  # most recently used last
+            out, y_len = run(x, lens, src, tgt, noise)
+        else:
+            cap = tyb * hop + hop - 1
+            xs = torch.zeros(bb, cap, device=self.device)
+            xs[:n, :x.shape[1]] = x
+            pad = [0] * (bb - n)
+            dev = self.device
+            nz = None
+            if noise is not None:
+                nz = torch.zeros(bb, self.inter_channels, tyb, device=dev)
+                nz[:n] = noise
+            out, y_len = self.model.convert_bucketed(
+                xs, torch.tensor(lens + pad, dtype=torch.int32).to(dev),
+                torch.tensor(src + pad, dtype=torch.long).to(dev),
+                torch.tensor(tgt + pad, dtype=torch.long).to(dev), nz, tyb, stft=stft)
+        if post is not None:
+            return post(out[:, 0], y_len), frames
+        return out, frames
+
+    def convert(self, wav, spkid_src, spkid_tgt, *, sampling_rate_in=None, noise_scale=0.0):
+        """Voice conversion: the recording ``wav`` (int16, scaled by 1 /
+        32768, or float in [-1, 1]; at ``sampling_rate_in``, default the
+        model's rate) of speaker spkid_src in the voice of spkid_tgt, as a
+        float32 waveform of (n // hop) * hop samples at the model's rate (n:
+        the samples at that rate).  One replay of a cached graph per call;
+        noise_scale > 0 samples the posterior (torch.randn on the device from
+        the generator this object owns), 0 takes its mean.  Raises
+        ValueError for a recording of more than 4096 frames or of at most
+        (n_fft - hop) / 2 samples, VitsAmdError on a CPU device."""
+        out, frames = self._convert_rows([wav], [spkid_src], [spkid_tgt], sampling_rate_in,
+                                         noise_scale)
+        return out[0, 0, :frames[0] * self.hop_size].cpu().numpy()
+
+    def convert_pcm(self, wav, spkid_src, spkid_tgt, *, sampling_rate_in=None, noise_scale=0.0,
+                    pitch=1.0, sampling_rate=None, volume=1.0, tail_silence=0.0):
+        """convert plus infer_pcm's output stage on the device (pitch /
+        sampling-rate resampling, volume, clip, int16, tail silence), the
+        length read from the graph's y_len; one device-to-host copy, of the
+        int16 PCM.  Returns (pcm int16 [n], n_model_samples)."""
+        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
+        tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
+        passes = self._post_passes(pitch, sampling_rate)
+        pcm, frames = self._convert_rows(
+            [wav], [spkid_src], [spkid_tgt], sampling_rate_in, noise_scale,
+            post=lambda w, y_len: self._post(w, passes, volume, tail, lengths=y_len,
+                                             length_scale=self.hop_size))
+        n = n_out = frames[0] * self.hop_size
+        for up, down in passes:
+            n_out = ops.resample_out_len(n_out, up, down)
+        return pcm[0, :n_out + tail].cpu().numpy(), n
+
+    def convert_pcm_batch(self, items, *, sampling_rate_in=None, noise_scale=0.0, pitch=1.0,
+                          sampling_rate=None, volume=1.0, tail_silence=0.0):
+        """convert_pcm for items = [(wav, spkid_src, spkid_tgt), ...] that
+        share the controls: (pcm int16 [total], offsets int64 [len + 1],
+        n_model list); item i's PCM, tail included, is
+        pcm[offsets[i]:offsets[i + 1]], byte for byte what convert_pcm returns
+        (at noise_scale 0; a draw's shape follows the batch).  A group of up
+        to MAX_BATCH items (batch buckets 2, 4, 8, 16) is one graph replay,
+        the post passes over its rows, the ragged pack and ONE device-to-host
+        copy."""
+        items = list(items)
+        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
+        tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
+        passes = self._post_passes(pitch, sampling_rate)
+        chunks, offsets, n_model = [], [0], []
+        for lo, hi in self._groups(len(items)):
+            if hi - lo == 1:
+                pcm, n = self.convert_pcm(*items[lo], sampling_rate_in=sampling_rate_in,
+                                          noise_scale=noise_scale, pitch=pitch,
+                                          sampling_rate=sampling_rate, volume=volume,
+                                          tail_silence=tail_silence)
+                chunks.append(pcm)
+                offsets.append(offsets[-1] + len(pcm))
+                n_model.append(n)
+                continue
+            n = hi - lo
+            bb = self._batch_bucket(n)
+
+            def post(w, y_len):
+                zeros = torch.zeros(bb + 1, device=w.device, dtype=torch.int32)
+                return self._post_pack(w, y_len, n, (y_len, zeros[:bb], zeros[bb:]), passes,
+                                       volume, tail)
+
+            packed, frames = self._convert_rows(
+                [w for w, _, _ in items[lo:hi]], [s for _, s, _ in items[lo:hi]],
+                [t for _, _, t in items[lo:hi]], sampling_rate_in, noise_scale, post=post)
+            header = -(-2 * (3 * bb + 2) // 8) * 8
+            row_cap = (packed.numel() - header) // bb  # (the padding rows hold nothing)
+            buf = self._to_host(packed[:header + n * row_cap])
+            offs = buf[:2 * (bb + 1)].view(np.int32)[:n + 1]
+            chunks.append(buf[header:header + int(offs[n])])
+            offsets += [offsets[-1] + int(o) for o in offs[1:]]
+            n_model += [f * self.hop_size for f in frames]
+        pcm = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int16)
+        return pcm, np.asarray(offsets, dtype=np.int64), n_model
 
     # text tokens are padded to a multiple of TX_BUCKET (masked encoder);
     # frame buckets are powers of two from 256 up to the noise buffer's 4096

@@ -182,9 +182,16 @@ class ResidualCouplingBlock(nn.Module):
 
     @torch.no_grad()
     def infer(self, x, g, reverse=True):
-        if not reverse:
-            raise NotImplementedError("infer() runs the reverse (generation) direction only")
-        return engine.flow_infer(self, x, g)
+        """The flow without a mask on the HIP plan.  reverse=True: generation
+        (models.py:228-235).  reverse=False: the forward flow as training
+        runs it, ``forward(x, ones, g, reverse=False)``: each mean-only
+        coupling adds its mean, x1 <- x1 + m(x0; g), then Flip - the exact
+        inverse of reverse=True.  This is NOT what the reference's
+        ``flow.infer(z, g, reverse=False)`` computes: its
+        ResidualCouplingLayer.infer (modules.py:362-375) ignores ``reverse``
+        and always subtracts, so that call is no forward flow (a round trip
+        through it is off by 47 % at the base config)."""
+        return engine.flow_infer(self, x, g, reverse=bool(reverse))
 
 
 class PosteriorEncoder(nn.Module):
@@ -720,6 +727,157 @@ class SynthesizerTrn(nn.Module):
         run.t_y = t_y
         run.batch = batch
         run.pool_len = P
+        return run
+
+    # ------------------------------------------------------- voice conversion
+    def _vc_core(self, spec, noise, lens, sid_src, sid_tgt, keep=False):
+        """spec [B, F, T] fp32 -> enc_q -> flow(g_src) -> flow^-1(g_tgt) ->
+        dec(g_tgt), every layer masked at lens (int32 [B], device); kernels
+        and the two embedding lookups only, no host sync.  Returns (o fp32
+        [B, 1, T * hop], (z, z_p, z_hat) when ``keep`` else None)."""
+        g_src = engine._f32(self.emb_g(sid_src))
+        g_tgt = engine._f32(self.emb_g(sid_tgt))
+        z, sl = engine.get_plan(self.enc_q, engine.PosteriorPlan).run_bucketed(
+            spec, noise, lens, stage_mult=self._stage_mult())
+        fplan = engine.get_plan(self.flow, engine.CouplingFlowPlan)
+        z_p = z.clone() if keep else z
+        fplan.run_(z_p, g_src, lengths=sl[0], forward=True)
+        z_hat = z_p.clone() if keep else z_p
+        fplan.run_(z_hat, g_tgt, lengths=sl[0])
+        o = engine.get_plan(self.dec, engine.GeneratorPlan).run(z_hat, g_tgt, lengths=sl[1:])
+        # the decoder's last conv runs unmasked over the whole buffer (its halo
+        # spills 3 samples past a row's end, and skipped tiles hold nothing
+        # meaningful): cut every row at lens * hop, zero behind
+        out = torch.empty_like(o)
+        engine.ops.resample_poly(o[:, 0], 1, 1, lengths=sl[0], length_scale=self.hop_total,
+                                 out=out[:, 0])
+        return out, ((z, z_p, z_hat) if keep else None)
+
+    @torch.no_grad()
+    def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, noise=None):
+        """Upstream VITS' ``voice_conversion``: the linear spectrogram y [B,
+        F, T] of speaker sid_src rendered in the voice of sid_tgt: z =
+        enc_q(y) (speaker-free), z_p = flow(z; g_src) (the forward flow,
+        see ResidualCouplingBlock.infer), z_hat = flow^-1(z_p; g_tgt), o_hat =
+        dec(z_hat; g_tgt).  ``noise`` [B, C, T], already scaled, is the
+        posterior draw (z = m + noise * exp(logs)); None gives the posterior
+        mean.  Rows are masked at y_lengths (latents zero past them, o_hat
+        zero past y_lengths * hop).  Exact-length and eager: this is the
+        definition convert_bucketed is held to, bit for bit.  Returns (o_hat
+        [B, 1, T * hop], y_mask [B, 1, T], (z, z_p, z_hat))."""
+        engine._check_gpu(y, "SynthesizerTrn.voice_conversion")
+        lens = y_lengths.to(device=y.device, dtype=torch.int32).contiguous()
+        o, zs = self._vc_core(engine._f32(y), noise, lens, sid_src, sid_tgt, keep=True)
+        y_mask = torch.unsqueeze(commons.sequence_mask(y_lengths.to(y.device), y.size(2)), 1).to(
+            y.dtype)
+        return o.to(y.dtype), y_mask, tuple(t.to(y.dtype) for t in zs)
+
+    def _vc_window(self, win, dev):
+        w = self.__dict__.get("_vc_win")
+        if w is None or w.numel() != win or w.device != dev:
+            w = self.__dict__["_vc_win"] = torch.hann_window(win, device=dev, dtype=torch.float32)
+        return w
+
+    @torch.no_grad()
+    def convert_bucketed(self, wav, n_samples, sid_src, sid_tgt, noise, t_y, *, stft):
+        """voice_conversion from the waveform with NO host synchronisation,
+        over a static bucket of t_y frames (capture_convert_bucketed makes it
+        one hipGraph).  wav [B, t_y * hop + hop - 1] fp32, n_samples int32
+        [B] on the device; noise [B, C, t_y] (pre-scaled) or None.
+
+        ``stft`` = (filter_length, hop_length, win_length) of the model's
+        data config, given to the call (spec_channels alone fixes neither
+        hop nor window; hop must equal the decoder's total upsampling).  The
+        spectrogram is mel_processing.spectrogram_torch's (reflect padding
+        (n_fft - hop) / 2 at each row's own end, eps 1e-6), computed per row
+        at its own length (ops.stft_mag_rows), so y_len = n_samples // hop
+        frames (0 for a row of at most (n_fft - hop) / 2 samples).  Every
+        layer runs masked at y_len under ops.length_skip(64).
+
+        Returns (wav_out fp32 [B, 1, t_y * hop], y_len int32 [B]): the first
+        y_len * hop samples of row b are bit for bit voice_conversion of that
+        row alone on its own exact-length spectrogram; the rest is zero."""
+        engine._check_gpu(wav, "SynthesizerTrn.convert_bucketed")
+        n_fft, hop, win = (int(v) for v in stft)
+        if hop != self.hop_total or n_fft // 2 + 1 != self.enc_q.in_channels:
+            raise ValueError(f"convert_bucketed: stft {tuple(stft)} does not fit a model of "
+                             f"{self.enc_q.in_channels} bins and hop {self.hop_total}")
+        B, cap = wav.shape
+        t_y = int(t_y)
+        if wav.dtype != torch.float32 or cap < t_y * hop:
+            raise ValueError(f"convert_bucketed: wav must be fp32 [B, >= {t_y * hop}], got "
+                             f"{wav.dtype} {tuple(wav.shape)}")
+        spec, y_len = engine.ops.stft_mag_rows(wav, n_samples, self._vc_window(win, wav.device),
+                                               n_fft, hop, win, t_y, pad=(n_fft - hop) // 2,
+                                               eps=1e-6)
+        with engine.ops.length_skip(64):
+            o, _ = self._vc_core(spec, noise, y_len, sid_src, sid_tgt)
+        return o, y_len
+
+    @torch.no_grad()
+    def capture_convert_bucketed(self, t_y, batch=1, warmup=2, *, stft):
+        """One hipGraph for convert_bucketed over [batch, t_y] (``stft`` as
+        there).  Returns run(wav, n_samples, sid_src, sid_tgt, noise=None) ->
+        (wav_out [batch, 1, t_y * hop], y_len [batch]), views of static
+        buffers: wav [n, <= t_y * hop + hop - 1] fp32 rows, n_samples /
+        sid_src / sid_tgt n host ints (or tensors), noise [n, C, t_y] or None
+        (the static noise is then zeroed: the posterior mean).  Rows at or
+        past n get length 0."""
+        dev = next(self.parameters()).device
+        n_fft, hop, win = (int(v) for v in stft)
+        t_y, batch = int(t_y), int(batch)
+        C = self.inter_channels
+        cap = t_y * hop + hop - 1
+        static = dict(wav=torch.zeros(batch, cap, device=dev),
+                      n=torch.zeros(batch, device=dev, dtype=torch.int32),
+                      src=torch.zeros(batch, device=dev, dtype=torch.long),
+                      tgt=torch.zeros(batch, device=dev, dtype=torch.long),
+                      noise=torch.zeros(batch, C, t_y, device=dev))
+        self._vc_window(win, dev)  # (built outside the capture)
+
+        def body():
+            return self.convert_bucketed(static["wav"], static["n"], static["src"], static["tgt"],
+                                         static["noise"], t_y, stft=(n_fft, hop, win))
+
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                body()
+        torch.cuda.current_stream(dev).wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = body()
+
+        def _ints(v, n, dtype):
+            t = torch.as_tensor(v, dtype=dtype).reshape(-1)[:n]
+            if t.numel() != n:
+                raise ValueError(f"convert replay: {n} rows need {n} values, got {t.numel()}")
+            return t
+
+        def run(wav, n_samples, sid_src, sid_tgt, noise=None):
+            n = wav.shape[0]
+            if not 1 <= n <= batch or wav.shape[1] > cap:
+                raise ValueError(f"convert replay: wav {tuple(wav.shape)} does not fit "
+                                 f"[{batch}, {cap}]")
+            static["wav"][:n, :wav.shape[1]].copy_(wav)
+            static["n"].zero_()
+            static["n"][:n].copy_(_ints(n_samples, n, torch.int32))
+            static["src"].zero_()
+            static["src"][:n].copy_(_ints(sid_src, n, torch.long))
+            static["tgt"].zero_()
+            static["tgt"][:n].copy_(_ints(sid_tgt, n, torch.long))
+            if noise is None:
+                static["noise"].zero_()
+            else:
+                static["noise"][:n].copy_(noise)
+            graph.replay()
+            return out
+
+        run.graph = graph
+        run.static = static
+        run.t_y = t_y
+        run.batch = batch
         return run
 
     # ------------------------------------------------------------ hipGraphs

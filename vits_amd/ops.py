@@ -1419,6 +1419,82 @@ def stft_mag(x: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int, win: i
     return _StftMag.apply(x.float(), window, n_fft, hop, win, pad, eps)
 
 
+def stft_rows_frames(length: int, n_fft: int, hop: int, pad: int,
+                     frames_cap: Optional[int] = None, cap: Optional[int] = None) -> int:
+    """Frames stft_mag_rows gives a row of ``length`` samples (the host
+    restatement of csrc/stft.hip stft_row_job)."""
+    L = max(0, int(length)) if cap is None else min(max(0, int(length)), int(cap))
+    if L <= pad or L + 2 * pad < n_fft:
+        return 0
+    frames = (L + 2 * pad - n_fft) // hop + 1
+    return frames if frames_cap is None else min(frames, int(frames_cap))
+
+
+def stft_mag_rows(x: torch.Tensor, lens: torch.Tensor, window: torch.Tensor, n_fft: int, hop: int,
+                  win: int, frames_cap: int, pad: Optional[int] = None, eps: float = 1e-7,
+                  out: Optional[torch.Tensor] = None, frames_out: Optional[torch.Tensor] = None):
+    """Magnitude STFT of a ragged batch without a host sync: x [B, cap] fp32
+    (rows may be strided), ``lens`` int32 [B] on the device.  Row b is
+    transformed at its own length clamp(lens[b], 0, cap) - the reflect padding
+    folds at its own end and nothing past it is read - into the first
+    frames_b columns of mag [B, n_fft//2+1, frames_cap], bit for bit
+    ``stft_mag`` of that row alone; later columns are 0.  Returns (mag,
+    frames int32 [B]).  Inference only (not differentiable)."""
+    if pad is None:
+        pad = n_fft // 2
+    require_device(x, lens, window)
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise _lib.VitsAmdError(f"stft_mag_rows: x must be fp32 [B, cap] with unit sample stride, "
+                                f"got {x.dtype} {tuple(x.shape)}")
+    B, cap = x.shape
+    if lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous():
+        raise _lib.VitsAmdError(f"stft_mag_rows: lens must be a contiguous int32 [{B}] tensor")
+    window = window.contiguous().float()
+    nb = n_fft // 2 + 1
+    if out is None:
+        out = torch.empty(B, nb, int(frames_cap), device=x.device, dtype=torch.float32)
+    if frames_out is None:
+        frames_out = torch.empty(B, device=x.device, dtype=torch.int32)
+    assert out.is_contiguous() and tuple(out.shape) == (B, nb, int(frames_cap))
+    assert frames_out.is_contiguous() and frames_out.dtype == torch.int32
+    check(_lib.load().vits_stft_mag_forward_rows(
+        x.data_ptr(), x.stride(0) if B > 1 else cap, B, cap, lens.data_ptr(), window.data_ptr(),
+        n_fft, hop, win, pad, eps, out.data_ptr(), int(frames_cap), frames_out.data_ptr(),
+        _stream_ptr(x.device)), "vits_stft_mag_forward_rows")
+    return out, frames_out
+
+
+def posterior_sample(m: torch.Tensor, s: torch.Tensor, noise: Optional[torch.Tensor],
+                     lens: torch.Tensor, noise_scale: float = 1.0, stage_mult=None,
+                     out: Optional[torch.Tensor] = None):
+    """z = m + noise * s * noise_scale for t < lens[b], 0 past it (noise None:
+    z = m); m, s [B, C, T] fp32 views with unit time stride and equal strides,
+    noise [B, C, T] contiguous, lens int32 [B].  With ``stage_mult`` also
+    returns the int32 [len(stage_mult), B] lengths lens[b] * stage_mult[i]
+    that the flow and decoder plans take (expand_durations' layout)."""
+    require_device(m, s, noise, lens)
+    B, Cc, T = m.shape
+    assert m.dtype == torch.float32 and s.dtype == torch.float32
+    assert m.stride() == s.stride() and m.stride(2) == 1
+    if lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous():
+        raise _lib.VitsAmdError(f"posterior_sample: lens must be a contiguous int32 [{B}] tensor")
+    if noise is not None:
+        noise = noise.float().contiguous()
+        assert tuple(noise.shape) == (B, Cc, T), noise.shape
+    if out is None:
+        out = torch.empty(B, Cc, T, device=m.device, dtype=torch.float32)
+    stage_lens, mult, n_stage = None, None, 0
+    if stage_mult is not None:
+        n_stage = len(stage_mult)
+        mult = (C.c_int32 * n_stage)(*[int(v) for v in stage_mult])
+        stage_lens = torch.empty(n_stage, B, device=m.device, dtype=torch.int32)
+    check(_lib.load().vits_posterior_sample(
+        m.data_ptr(), s.data_ptr(), m.stride(0), m.stride(1), _ptr(noise), float(noise_scale),
+        lens.data_ptr(), out.data_ptr(), B, Cc, T, _ptr(stage_lens), mult, n_stage,
+        _stream_ptr(m.device)), "vits_posterior_sample")
+    return out if stage_mult is None else (out, stage_lens)
+
+
 # ---------------------------------------------------------------------------
 # PCM output stage: polyphase resampler + int16 epilogue (csrc/post.hip)
 # ---------------------------------------------------------------------------

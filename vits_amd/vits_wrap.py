@@ -195,6 +195,40 @@ class VITSWrap(object):
         return out
 
     @torch.no_grad()
+    def converting(self, inputs: dict) -> dict:
+        """Voice conversion request: {"wav" (int16 or float samples),
+        "sampling_rate_in", "spkid_src", "spkid_tgt", "pitch",
+        "sampling_rate", "volume", "tail_silence", "id"} -> the dict of
+        ``speaking`` without its text fields: "wav" (RIFF bytes), "sr",
+        "segment_info" (one entry, start_ms / end_ms), the times and rtf.
+        Clamps as in ``speaking``.  Needs device_post=True: the recording is
+        converted and post-processed on the GPU (EmoVITS.convert_pcm) and only
+        the int16 PCM comes back."""
+        if not self.device_post:
+            raise ValueError("VITSWrap.converting needs device_post=True on a ROCm GPU")
+        volume = max(0.0, min(1.0, float(inputs.get("volume", self.default_volume))))
+        pitch = max(0.5, min(2.0, float(inputs.get("pitch", self.default_pitch))))
+        sampling_rate = min(48000, max(8000, int(inputs.get("sampling_rate",
+                                                            self.default_sampling_rate))))
+        tail_silence = float(inputs.get("tail_silence", self.default_tail_silece))
+        inputs.setdefault("id", str(time.time()).replace(".", "_"))
+        spkid_tgt = int(inputs.get("spkid_tgt", self.default_spkid))
+        t0 = time.time()
+        pcm, n_model = self.speecher.convert_pcm(
+            inputs["wav"], int(inputs["spkid_src"]), spkid_tgt,
+            sampling_rate_in=inputs.get("sampling_rate_in"), pitch=pitch,
+            sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence)
+        t_back = time.time() - t0
+        out = inputs
+        out["wav"] = _gen_wav_header(len(pcm), sampling_rate, 16) + pcm.tobytes()
+        out["sr"] = sampling_rate
+        out["segment_info"] = [{"start_ms": 0.0, "end_ms": len(pcm) / sampling_rate * 1000}]
+        out["time_used_frontend"] = 0.0
+        out["time_used_backend"] = t_back * 1000
+        out["rtf"] = t_back / max(1e-9, n_model / self.default_sampling_rate)
+        return out
+
+    @torch.no_grad()
     def speaking_many(self, list_of_inputs) -> list:
         """``speaking`` for several requests at once: one dict per input, the
         same ``wav``, ``sr`` and ``segment_info`` as ``[speaking(i) for i in
