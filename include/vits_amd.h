@@ -689,6 +689,66 @@ int vits_resblock_pair_f32p_forward(const vits_resblock_pair_desc* d, int n, int
 int vits_resblock_pair_f32p_mean_forward(const vits_resblock_pair_desc* d, int n, int batch,
                                          void* stream);
 
+/* ---------------------------------------------------------------------- */
+/* One WN layer (modules.py:130-182) of an fp32 model as ONE kernel, in    */
+/* the split-fp32 arithmetic (VITS_WDT_F32P; csrc/wn_f32p.hip):            */
+/*   g = tanh(a) * sigmoid(b),  (a|b) = in_layer(h) + b1 + cond            */
+/*   rs = res_skip(g) + b2;  h_out = h + rs[:H];  skip (+)= rs[H:]         */
+/*   last layer: res_skip has H rows, skip (+)= rs, h_out = NULL           */
+/* w1 = Conv1d(H, 2H, k, dil, 'same' padding) in the GATE row layout, w2   */
+/* the 1x1 res_skip: the pre-split images [cin_pad/16][k][2][3][m_pad][8]  */
+/* bf16 of vits_conv1d_desc; b1 / cond in logical order ([a | b], cond     */
+/* already offset to this layer).  Bitwise the two launches it replaces    */
+/* (in_layer with the gate epilogue, res_skip with the res + skip one).    */
+/* h, h_out, skip: [B][H][T] fp32, time-contiguous; h 16-byte aligned with */
+/* strides % 4 == 0, T % 4 == 0.  h_out and skip must not alias h: other   */
+/* workgroups read h's halo columns.  hidden == 256, odd k, (k - 1) * dil  */
+/* <= 64.  lengths: outputs are 0 at t >= lengths[b] (g is not masked, as  */
+/* the gate conv); len_skip as vits_conv1d_desc.len_skip.  ng: columns per */
+/* workgroup, 32 or 64; 0 = chosen by grid size (no bit depends on it).    */
+/* ---------------------------------------------------------------------- */
+typedef struct vits_wn_layer_desc {
+  const float* h;
+  int64_t h_bstride;
+  int32_t h_cstride;
+  int32_t t_len;
+  int32_t hidden;
+  int32_t k;
+  int32_t dil;
+  int32_t last;
+  const void* w1;
+  int32_t m_pad1;
+  int32_t cin_pad1;
+  const float* b1;
+  const float* cond;
+  int64_t cond_bstride;
+  const void* w2;
+  int32_t m_pad2;
+  int32_t cin_pad2;
+  const float* b2;
+  float* h_out;
+  int64_t ho_bstride;
+  int32_t ho_cstride;
+  int32_t accumulate;    /* skip += (every layer but the first)              */
+  float* skip;
+  int64_t skip_bstride;
+  int32_t skip_cstride;
+  int32_t len_skip;
+  int32_t ng;
+  int32_t reserved;
+  const int32_t* lengths;
+} vits_wn_layer_desc;
+/* n layers in order (a WN stack), one host call.  Every descriptor is     */
+/* checked before the first launch.                                        */
+int vits_wn_layers_f32p_forward(const vits_wn_layer_desc* d, int n, int batch, void* stream);
+/* Convs and fused WN layers in one ordered host call (a coupling's pre /  */
+/* WN stack / post): kinds[i] = 0 takes the next of convs, 1 the next of   */
+/* wn; n items in all, nconv + nwn == n.  Every descriptor is checked      */
+/* before the first launch.                                                */
+int vits_conv1d_wn_seq_forward(const vits_conv1d_desc* convs, int nconv,
+                               const vits_wn_layer_desc* wn, int nwn, const int32_t* kinds, int n,
+                               int batch, void* stream);
+
 /* Fused RAdam step (radam.py:35-99, the D optimizer of train_stft.py:97) */
 /* over a list of fp32 tensors, one launch per VITS_RADAM_MAX tensors.     */
 /* scal: device float[8] state (scal[0] = step count, the rest scratch);  */

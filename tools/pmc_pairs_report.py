@@ -13,13 +13,18 @@ import sys
 from collections import defaultdict
 
 base = sys.argv[1] if len(sys.argv) > 1 else "bench_logs/pmc_pairs"
-KEY = "resblock_f32p_kernel"
+# KEY=wn_layer_f32p_kernel: the same report for the fused WN layer kernel
+# (csrc/wn_f32p.hip; instances <H, NG>)
+KEY = os.environ.get("KEY", "resblock_f32p_kernel")
 # fused pair launches of one infer_p2 step (9 per stage pair index and
 # accumulating launch; override when the plan changes)
 LAST = int(os.environ.get("LAST", "0"))
 
 
 def inst(name):
+    if KEY != "resblock_f32p_kernel":
+        m = re.search(KEY + r"<([^>]*)>", name)
+        return f"{KEY}<{m.group(1).replace(' ', '')}>" if m else name
     m = re.search(KEY + r"<(\d+)", name)
     return f"{KEY}<{m.group(1)},0>" if m else name
 

@@ -117,6 +117,41 @@ class ResblockPairDesc(C.Structure):
     ]
 
 
+class WnLayerDesc(C.Structure):
+    """include/vits_amd.h vits_wn_layer_desc."""
+    _fields_ = [
+        ("h", C.c_void_p),
+        ("h_bstride", C.c_int64),
+        ("h_cstride", C.c_int32),
+        ("t_len", C.c_int32),
+        ("hidden", C.c_int32),
+        ("k", C.c_int32),
+        ("dil", C.c_int32),
+        ("last", C.c_int32),
+        ("w1", C.c_void_p),
+        ("m_pad1", C.c_int32),
+        ("cin_pad1", C.c_int32),
+        ("b1", C.c_void_p),
+        ("cond", C.c_void_p),
+        ("cond_bstride", C.c_int64),
+        ("w2", C.c_void_p),
+        ("m_pad2", C.c_int32),
+        ("cin_pad2", C.c_int32),
+        ("b2", C.c_void_p),
+        ("h_out", C.c_void_p),
+        ("ho_bstride", C.c_int64),
+        ("ho_cstride", C.c_int32),
+        ("accumulate", C.c_int32),
+        ("skip", C.c_void_p),
+        ("skip_bstride", C.c_int64),
+        ("skip_cstride", C.c_int32),
+        ("len_skip", C.c_int32),
+        ("ng", C.c_int32),
+        ("reserved", C.c_int32),
+        ("lengths", C.c_void_p),
+    ]
+
+
 class StftJob(C.Structure):
     _fields_ = [
         ("x", C.c_void_p),
@@ -379,6 +414,11 @@ _SIGS = {
         C.c_int, [C.POINTER(ResblockPairDesc), C.c_int, C.c_int, C.c_void_p]),
     "vits_resblock_pair_f32p_mean_forward": (
         C.c_int, [C.POINTER(ResblockPairDesc), C.c_int, C.c_int, C.c_void_p]),
+    "vits_wn_layers_f32p_forward": (
+        C.c_int, [C.POINTER(WnLayerDesc), C.c_int, C.c_int, C.c_void_p]),
+    "vits_conv1d_wn_seq_forward": (
+        C.c_int, [C.POINTER(ConvDesc), C.c_int, C.POINTER(WnLayerDesc), C.c_int,
+                  C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p]),
     "vits_resblock_pair_kc": (
         C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vits_resblock_pair16_forward": (

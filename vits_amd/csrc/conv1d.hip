@@ -140,6 +140,31 @@ extern "C" int vits_conv1d_forward_seq(const vits_conv1d_desc* d, int n, int bat
   return VITS_OK;
 }
 
+// fused WN layers (wn_f32p.hip)
+int vits_wn_layer_check(const vits_wn_layer_desc& d, int batch);
+int vits_wn_layer_launch(const vits_wn_layer_desc& d, int batch, hipStream_t s);
+
+extern "C" int vits_conv1d_wn_seq_forward(const vits_conv1d_desc* convs, int nconv,
+                                          const vits_wn_layer_desc* wn, int nwn,
+                                          const int32_t* kinds, int n, int batch, void* stream) {
+  if (!kinds || n < 1 || nconv < 0 || nwn < 0 || nconv + nwn != n) return VITS_E_ARG;
+  if ((nconv > 0 && !convs) || (nwn > 0 && !wn)) return VITS_E_ARG;
+  int ic = 0, iw = 0;
+  for (int i = 0; i < n; ++i) {  // every item is checked before the first launch
+    VITS_CHECK_ARG(kinds[i] == 0 || kinds[i] == 1);
+    VITS_CHECK_ARG(kinds[i] ? iw < nwn : ic < nconv);
+    const int rc = kinds[i] ? vits_wn_layer_check(wn[iw++], batch) : check_desc(convs[ic++], batch);
+    if (rc) return rc;
+  }
+  ic = iw = 0;
+  for (int i = 0; i < n; ++i) {
+    const int rc = kinds[i] ? vits_wn_layer_launch(wn[iw++], batch, as_stream(stream))
+                            : conv1d_group(convs + ic++, 1, batch, as_stream(stream));
+    if (rc) return rc;
+  }
+  return VITS_OK;
+}
+
 extern "C" int vits_conv1d_forward_groups(const vits_conv1d_desc* d, const int32_t* sizes,
                                           int ngroups, int batch, void* stream) {
   if (!d || !sizes || ngroups < 0) return VITS_E_ARG;

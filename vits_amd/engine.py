@@ -140,6 +140,10 @@ MEAN_PAIRS16 = True
 # fp32 models: the same for the split-fp32 pairs of the 32-channel stage
 # (vits_resblock_pair_f32p_mean_forward; bitwise the accumulating launches)
 MEAN_PAIRS_F32P = True
+# fused WN layers (csrc/wn_f32p.hip) in the flow and the posterior encoder of
+# a split-fp32 model (False: the two-conv path, for A/B timing and the parity
+# tests of both)
+_FUSED_WN = True
 # 16-bit models keep the decoder's activations 16-bit in HBM (as the
 # reference's .half() model holds them): every conv of the Generator reads and
 # writes its own 16-bit type (io16), halving the stage traffic.  C5 (B=4,
@@ -347,12 +351,34 @@ class WNPlan:
             w, b = _conv_eff(wn.res_skip_layers[i])
             self.res_skip.append(pack_conv(w, b))
 
+    def fused(self, h: torch.Tensor) -> bool:
+        """Whether every layer runs as one fused launch on h (csrc/wn_f32p.hip)."""
+        return _FUSED_WN and all(ops.wn_layer_f32p_supported(a, r, h)
+                                 for a, r in zip(self.in_layers, self.res_skip))
+
     def descs(self, h: torch.Tensor, skip: torch.Tensor, abuf: torch.Tensor,
               cond: Optional[torch.Tensor], lengths: Optional[torch.Tensor]):
-        """h [B,H,T] is updated in place (residual stream), skip receives the
-        WN output (masked at the last layer when lengths are given)."""
+        """The stack's launches, for ops.conv1d_launch_seq: skip receives the
+        WN output (masked when lengths are given).  Fused layers (where
+        ``fused(h)``): one launch each, the residual stream alternating
+        between h and abuf - a layer's neighbouring workgroups still read the
+        halo of its input, so it is never updated in place.  Otherwise the
+        two-conv path: in_layer gates into abuf, res_skip updates h in place.
+        ``final_h`` tells where the residual stream ends."""
         H = self.H
         out = []
+        if self.fused(h):
+            cur, nxt = h, abuf
+            for i in range(self.n_layers):
+                coff = 0 if self.cond_off is None else self.cond_off + 2 * H * i
+                last = i == self.n_layers - 1
+                out.append(ops.wn_layer_desc(
+                    self.in_layers[i], self.res_skip[i], cur, None if last else nxt, skip,
+                    accumulate=i > 0, cond=cond if self.cond_off is not None else None,
+                    cond_offset=coff, lengths=lengths))
+                if not last:
+                    cur, nxt = nxt, cur
+            return out
         for i in range(self.n_layers):
             coff = 0 if self.cond_off is None else self.cond_off + 2 * H * i
             out.append(make_desc(self.in_layers[i], h, make_out(abuf),
@@ -368,6 +394,11 @@ class WNPlan:
                 out.append(make_desc(self.res_skip[i], abuf,
                                      make_out(skip, accumulate=i > 0), lengths=lengths))
         return out
+
+    def final_h(self, h: torch.Tensor, abuf: torch.Tensor) -> torch.Tensor:
+        """The buffer that holds the residual stream after ``descs`` ran (the
+        last layer does not update it)."""
+        return abuf if self.fused(h) and self.n_layers % 2 == 0 else h
 
 
 # ---------------------------------------------------------------------------

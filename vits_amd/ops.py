@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_NONE, WDT_BF16, WDT_F16, WDT_F32, WDT_F32P, WDT_F32S, ConvDesc, ConvOut, EPI_GATE, EPI_STORE,
-                   ResblockPairDesc,
+                   ResblockPairDesc, WnLayerDesc,
                    EPI_UPSAMPLE, TILE_128x128, TILE_32x256, TILE_64x128, TILE_64x256, TILE_ROWS,
                    check)
 
@@ -600,6 +600,21 @@ class ConvTimer:
         self.shapes.append("pair " + "+".join(
             f"C{d.channels}k{d.k}d{d.dil}T{d.t_len}" for d in group))
 
+    def launch_wn(self, lib, desc, batch, device):
+        """One fused WN layer: the FLOPs of the two convs it replaces, at the
+        split-fp32 peak."""
+        s = torch.cuda.Event(enable_timing=True)
+        e = torch.cuda.Event(enable_timing=True)
+        stream = torch.cuda.current_stream(device)
+        s.record(stream)
+        check(lib.vits_wn_layers_f32p_forward(C.byref(desc), 1, batch, stream.cuda_stream),
+              "vits_wn_layers_f32p_forward")
+        e.record(stream)
+        self.records.append((s, e, wn_layer_flops(desc, batch)))
+        self.peaks.append(MFMA_PEAK_TFLOPS[WDT_F32S])
+        self.shapes.append(f"wn H{desc.hidden}k{desc.k}d{desc.dil}T{desc.t_len}"
+                           + ("last" if desc.last else ""))
+
     def summary(self):
         torch.cuda.synchronize()
         ms = [s.elapsed_time(e) for s, e, _ in self.records]
@@ -805,6 +820,71 @@ def resblock_pair_launch(descs, batch: int, device: torch.device, wdtype: int = 
           "vits_resblock_pair_forward")
 
 
+# ---------------------------------------------------------------------------
+# fused WN layer (csrc/wn_f32p.hip)
+# ---------------------------------------------------------------------------
+# columns per workgroup of the fused WN layer: 0 = chosen by grid size in the
+# library, 32 / 64 force a tile (tools/wn_bench.py, the tests: no bit depends
+# on it)
+WN_NG = 0
+
+
+def wn_layer_f32p_supported(in_layer: PackedConv, res_skip: PackedConv, h: torch.Tensor) -> bool:
+    """WN layers of an fp32 model that run fused (csrc/wn_f32p.hip): both
+    convs pre-split (VITS_WDT_F32P), H = 256, in_layer Conv1d(H, 2H, odd k,
+    'same' padding) with the gate epilogue, res_skip 1x1 with 2H rows (last
+    layer: H), 16-byte aligned fp32 time rows with T % 4 == 0.  Anything else
+    keeps the two-conv path."""
+    H = in_layer.cin
+    return (in_layer.wdtype == WDT_F32P and res_skip.wdtype == WDT_F32P and H == 256
+            and h.dtype == torch.float32 and h.dim() == 3 and h.shape[1] == H
+            and in_layer.m == 2 * H and in_layer.epi == EPI_GATE and in_layer.cin_pad == H
+            and in_layer.k % 2 == 1 and (in_layer.k - 1) * in_layer.dil <= 56
+            and in_layer.pad_left == (in_layer.k - 1) * in_layer.dil // 2
+            and res_skip.epi == EPI_STORE and res_skip.k == 1 and res_skip.cin == H
+            and res_skip.cin_pad == H and res_skip.m in (H, 2 * H) and res_skip.pad_left == 0
+            and h.shape[2] % 4 == 0 and h.stride(2) == 1 and h.stride(1) % 4 == 0
+            and h.stride(0) % 4 == 0 and h.data_ptr() % 16 == 0
+            and H * h.stride(1) < 2 ** 31)
+
+
+def wn_layer_desc(in_layer: PackedConv, res_skip: PackedConv, h: torch.Tensor,
+                  h_out: Optional[torch.Tensor], skip: torch.Tensor, *, accumulate: bool,
+                  cond: Optional[torch.Tensor] = None, cond_offset: int = 0,
+                  lengths: Optional[torch.Tensor] = None) -> WnLayerDesc:
+    """One fused WN layer: h_out = h + res, skip (+)= skip part; h_out None:
+    the last layer (res_skip has H rows, all to skip).  h_out and skip must
+    not be h."""
+    H, T = h.shape[1], h.shape[2]
+    last = h_out is None
+    assert res_skip.m == (H if last else 2 * H)
+    assert skip.dtype == torch.float32 and skip.stride(2) == 1
+    d = WnLayerDesc()
+    d.h, d.h_bstride, d.h_cstride, d.t_len = h.data_ptr(), h.stride(0), h.stride(1), T
+    d.hidden, d.k, d.dil, d.last = H, in_layer.k, in_layer.dil, int(last)
+    d.w1, d.m_pad1, d.cin_pad1 = in_layer.w.data_ptr(), in_layer.m_pad, in_layer.cin_pad
+    d.b1 = _ptr(in_layer.bias)
+    if cond is not None:
+        d.cond, d.cond_bstride = cond.data_ptr() + 4 * cond_offset, cond.stride(0)
+    d.w2, d.m_pad2, d.cin_pad2 = res_skip.w.data_ptr(), res_skip.m_pad, res_skip.cin_pad
+    d.b2 = _ptr(res_skip.bias)
+    if not last:
+        assert h_out.dtype == torch.float32 and h_out.stride(2) == 1
+        d.h_out, d.ho_bstride, d.ho_cstride = h_out.data_ptr(), h_out.stride(0), h_out.stride(1)
+    d.skip, d.skip_bstride, d.skip_cstride = skip.data_ptr(), skip.stride(0), skip.stride(1)
+    d.accumulate = int(accumulate)
+    d.lengths = _ptr(lengths)
+    d.len_skip = LEN_SKIP.margin if lengths is not None else 0
+    d.ng = WN_NG
+    return d
+
+
+def wn_layer_flops(d: WnLayerDesc, batch: int) -> int:
+    """Algorithmic FLOPs of the layer: those of the two convs it replaces."""
+    H = d.hidden
+    return 2 * batch * d.t_len * (2 * H * H * d.k + (H if d.last else 2 * H) * H)
+
+
 def conv1d_launch(desc: ConvDesc, batch: int, device: torch.device):
     lib = _lib.load()
     if ConvTimer.active is not None:
@@ -815,11 +895,26 @@ def conv1d_launch(desc: ConvDesc, batch: int, device: torch.device):
 def conv1d_launch_seq(descs, batch: int, device: torch.device):
     """Run descriptors in order, one host call.  An item may be a tuple of
     independent ConvDescs (the ResBlock2 branches of one Generator stage):
-    they share one launch (vits_conv1d_forward_groups)."""
+    they share one launch (vits_conv1d_forward_groups).  A sequence that holds
+    fused WN layers (WnLayerDesc, between single ConvDescs) is one call of
+    vits_conv1d_wn_seq_forward."""
     lib = _lib.load()
     if ConvTimer.active is not None:
         for d in descs:
-            ConvTimer.active.launch(lib, d, batch, device)
+            if isinstance(d, WnLayerDesc):
+                ConvTimer.active.launch_wn(lib, d, batch, device)
+            else:
+                ConvTimer.active.launch(lib, d, batch, device)
+        return
+    if any(isinstance(d, WnLayerDesc) for d in descs):
+        convs = [d for d in descs if not isinstance(d, WnLayerDesc)]
+        wns = [d for d in descs if isinstance(d, WnLayerDesc)]
+        assert all(isinstance(d, ConvDesc) for d in convs), "no grouped launches beside WN layers"
+        kinds = (C.c_int32 * len(descs))(*[int(isinstance(d, WnLayerDesc)) for d in descs])
+        check(lib.vits_conv1d_wn_seq_forward((ConvDesc * len(convs))(*convs), len(convs),
+                                             (WnLayerDesc * len(wns))(*wns), len(wns), kinds,
+                                             len(descs), batch, _stream_ptr(device)),
+              "vits_conv1d_wn_seq_forward")
         return
     flat, sizes = [], []
     for d in descs:
