@@ -1007,6 +1007,29 @@ int vits_amd_device_arch(char* buf, int len);
 int64_t vits_dispatch_count(int which);
 void vits_dispatch_count_reset(void);
 
+/* Test hook: which conv kernel vits_conv1d_forward / one shared-grid group */
+/* of vits_conv1d_forward_groups would launch for d[0..n) at `batch`.  It   */
+/* runs the launch path itself (descriptor checks, global-A choice, small-  */
+/* grid fallback, staging kind, budgets) up to the launch and stops there:  */
+/* a plain host function - no device needed, no pointer dereferenced (their */
+/* values are read for alignment only), no dispatch counter bumped.         */
+/* Returns what the launch would: VITS_OK with *out filled, or the refusal */
+/* (VITS_E_UNSUP for mixed staging kinds or an over-budget chunk, ...).     */
+#define VITS_PLAN_EPI_STORE2 3  /* plan.epi: STORE with two outputs (split < m) */
+typedef struct vits_conv1d_plan_t {
+  int32_t wdtype;    /* VITS_WDT_* of the kernel                             */
+  int32_t ga;        /* 16-bit kinds: weight fragments read from global memory */
+  int32_t bm, bn;    /* workgroup tile (after the small-grid fallback)       */
+  int32_t waves_m, waves_n;
+  int32_t v4;        /* 16-byte-block X staging (else element-wise)          */
+  int32_t io16;      /* 16-bit activations                                    */
+  int32_t epi;       /* VITS_EPI_*, or VITS_PLAN_EPI_STORE2                  */
+  int32_t up_lds;    /* UPSAMPLE: the LDS-staged plain store is taken        */
+  int32_t lds_bytes; /* dynamic LDS of the launch                            */
+  int32_t grid[3];
+} vits_conv1d_plan_t;
+int vits_conv1d_plan(const vits_conv1d_desc* d, int n, int batch, vits_conv1d_plan_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,27 @@ class ConvDesc(C.Structure):
     ]
 
 
+PLAN_EPI_STORE2 = 3
+
+
+class ConvPlan(C.Structure):
+    """include/vits_amd.h vits_conv1d_plan_t."""
+    _fields_ = [
+        ("wdtype", C.c_int32),
+        ("ga", C.c_int32),
+        ("bm", C.c_int32),
+        ("bn", C.c_int32),
+        ("waves_m", C.c_int32),
+        ("waves_n", C.c_int32),
+        ("v4", C.c_int32),
+        ("io16", C.c_int32),
+        ("epi", C.c_int32),
+        ("up_lds", C.c_int32),
+        ("lds_bytes", C.c_int32),
+        ("grid", C.c_int32 * 3),
+    ]
+
+
 class ResblockPairDesc(C.Structure):
     """include/vits_amd.h vits_resblock_pair_desc."""
     _fields_ = [
@@ -524,6 +545,7 @@ _SIGS = {
     "vits_amd_device_arch": (C.c_int, [C.c_char_p, C.c_int]),
     "vits_dispatch_count": (C.c_int64, [C.c_int]),
     "vits_dispatch_count_reset": (None, []),
+    "vits_conv1d_plan": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.POINTER(ConvPlan)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -29,6 +29,11 @@
 
 #include "conv1d_impl.h"
 
+namespace vits_conv {
+static thread_local vits_conv1d_plan_t* g_plan_target = nullptr;
+vits_conv1d_plan_t* plan_target() { return g_plan_target; }
+}  // namespace vits_conv
+
 namespace {
 
 int check_desc(const vits_conv1d_desc& d, int batch) {
@@ -106,7 +111,7 @@ int conv1d_group(const vits_conv1d_desc* d, int n, int batch, hipStream_t s) {
       rc = vits_conv1d_dispatch_f32(g, s);
       which = VITS_CNT_CONV_F32;
   }
-  if (rc == VITS_OK) vits_count(which);
+  if (rc == VITS_OK && !vits_conv::plan_target()) vits_count(which);
   return rc;
 }
 
@@ -129,6 +134,18 @@ int conv1d_group_or_seq(const vits_conv1d_desc* d, int n, int batch, hipStream_t
 extern "C" int vits_conv1d_forward(const vits_conv1d_desc* d, int batch, void* stream) {
   if (!d) return VITS_E_ARG;
   return conv1d_group(d, 1, batch, as_stream(stream));
+}
+
+// the launch path itself with the thread's plan target set: launch_tile_v
+// fills it and returns where it would have launched
+extern "C" int vits_conv1d_plan(const vits_conv1d_desc* d, int n, int batch,
+                                vits_conv1d_plan_t* out) {
+  if (!d || !out || n < 1 || n > vits_conv::VITS_CONV_GROUP) return VITS_E_ARG;
+  *out = vits_conv1d_plan_t{};
+  vits_conv::g_plan_target = out;
+  const int rc = conv1d_group(d, n, batch, nullptr);
+  vits_conv::g_plan_target = nullptr;
+  return rc;
 }
 
 extern "C" int vits_conv1d_forward_seq(const vits_conv1d_desc* d, int n, int batch, void* stream) {

@@ -1287,6 +1287,10 @@ __global__ __launch_bounds__(256, (WT == VITS_WDT_F32S || WT == VITS_WDT_F32P) ?
   }
 }
 
+// vits_conv1d_plan (conv1d.hip): non-null while the calling thread is planning;
+// launch_tile_v then fills it with what it was about to launch and returns
+vits_conv1d_plan_t* plan_target();
+
 template <int BM, int BN, int WM_, int WN_, int WT, bool V4, bool IO16, bool GA = false>
 int launch_tile_v(const ConvGroup& g, hipStream_t s, const size_t* xrs) {
   constexpr bool BF = WT != VITS_WDT_F32;
@@ -1336,22 +1340,47 @@ int launch_tile_v(const ConvGroup& g, hipStream_t s, const size_t* xrs) {
   dim3 grid(gx, gy, g.n * g.batch);
   dim3 block(256);
   const vits_conv1d_desc& d = g.d[0];
+  void (*kern)(const ConvGroup) = nullptr;
+  int epi = d.epi;
   switch (d.epi) {
     case VITS_EPI_STORE:
-      if (d.split < d.m)
-        hipLaunchKernelGGL((conv1d_mfma_kernel<BM, BN, WM_, WN_, EPI_STORE2, WT, V4, IO16, GA>), grid, block, lds, s, g);
-      else
-        hipLaunchKernelGGL((conv1d_mfma_kernel<BM, BN, WM_, WN_, VITS_EPI_STORE, WT, V4, IO16, GA>), grid, block, lds, s, g);
+      if (d.split < d.m) {
+        kern = conv1d_mfma_kernel<BM, BN, WM_, WN_, EPI_STORE2, WT, V4, IO16, GA>;
+        epi = VITS_PLAN_EPI_STORE2;
+      } else {
+        kern = conv1d_mfma_kernel<BM, BN, WM_, WN_, VITS_EPI_STORE, WT, V4, IO16, GA>;
+      }
       break;
     case VITS_EPI_GATE:
-      hipLaunchKernelGGL((conv1d_mfma_kernel<BM, BN, WM_, WN_, VITS_EPI_GATE, WT, V4, IO16, GA>), grid, block, lds, s, g);
+      kern = conv1d_mfma_kernel<BM, BN, WM_, WN_, VITS_EPI_GATE, WT, V4, IO16, GA>;
       break;
     case VITS_EPI_UPSAMPLE:
-      hipLaunchKernelGGL((conv1d_mfma_kernel<BM, BN, WM_, WN_, VITS_EPI_UPSAMPLE, WT, V4, IO16, GA>), grid, block, lds, s, g);
+      kern = conv1d_mfma_kernel<BM, BN, WM_, WN_, VITS_EPI_UPSAMPLE, WT, V4, IO16, GA>;
       break;
     default:
       return VITS_E_UNSUP;
   }
+  if (vits_conv1d_plan_t* pl = plan_target()) {  // vits_conv1d_plan: report, launch nothing
+    pl->wdtype = WT;
+    pl->ga = GA;
+    pl->bm = BM;
+    pl->bn = BN;
+    pl->waves_m = WM_;
+    pl->waves_n = WN_;
+    pl->v4 = V4;
+    pl->io16 = IO16;
+    pl->epi = epi;
+    // (the kernel's own test for the LDS-staged plain upsample store, a
+    // device-side branch on the descriptor: see its UPSAMPLE epilogue)
+    pl->up_lds = d.epi == VITS_EPI_UPSAMPLE && d.out0.act == VITS_ACT_NONE && !d.out0.res &&
+                 !d.out0.accumulate && d.out0.post_div == 1.0f;
+    pl->lds_bytes = (int32_t)lds;
+    pl->grid[0] = gx;
+    pl->grid[1] = gy;
+    pl->grid[2] = g.n * g.batch;
+    return VITS_OK;
+  }
+  hipLaunchKernelGGL(kern, grid, block, lds, s, g);
   return vits_launch_status();
 }
 

@@ -892,6 +892,28 @@ def conv1d_launch(desc: ConvDesc, batch: int, device: torch.device):
     check(lib.vits_conv1d_forward(C.byref(desc), batch, _stream_ptr(device)), "vits_conv1d_forward")
 
 
+PLAN_FIELDS = ("wdtype", "ga", "bm", "bn", "waves_m", "waves_n", "v4", "io16", "epi", "up_lds",
+               "lds_bytes")
+
+
+def conv1d_plan(descs, batch: int):
+    """Which kernel conv1d_launch / one shared-grid tuple of conv1d_launch_seq
+    would run for ``descs`` (a ConvDesc or up to three) at ``batch``: the
+    library's own launch path stopped before the launch
+    (vits_conv1d_plan; host only - no device, nothing read through the
+    pointers).  Returns ``(rc, plan)``: rc is the status the launch would
+    return, plan a dict of PLAN_FIELDS plus ``grid`` (None when refused)."""
+    group = tuple(descs) if isinstance(descs, (tuple, list)) else (descs,)
+    arr = (ConvDesc * len(group))(*group)
+    out = _lib.ConvPlan()
+    rc = _lib.load().vits_conv1d_plan(arr, len(group), batch, C.byref(out))
+    if rc != _lib.VITS_OK:
+        return rc, None
+    plan = {f: int(getattr(out, f)) for f in PLAN_FIELDS}
+    plan["grid"] = tuple(out.grid)
+    return rc, plan
+
+
 def conv1d_launch_seq(descs, batch: int, device: torch.device):
     """Run descriptors in order, one host call.  An item may be a tuple of
     independent ConvDescs (the ResBlock2 branches of one Generator stage):
