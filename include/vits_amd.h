@@ -315,6 +315,27 @@ int vits_maximum_path_lengths(const float* neg_cent, const int32_t* t_t_len,
 /* bytes of workspace the two calls above need (0 when the backtrack bits */
 /* fit in LDS)                                                            */
 int64_t vits_maximum_path_workspace(int batch, int t_t, int t_s);
+/* Forced alignment: the same DP and backtrack as vits_maximum_path_lengths  */
+/* (same neg_cent, lengths and workspace), but no path is written.  From the */
+/* path of row b:                                                            */
+/*   durations[b][x]   frames y < t_t_len[b] on token x; 0 for x >=          */
+/*                     t_s_len[b]                                            */
+/*   scores[b][x]      (or NULL) the fp32 sum of neg_cent[b][y][x] over the  */
+/*                     token's frames, added one by one in increasing y from */
+/*                     0.0f (no FMA, no tree: a float32 loop reproduces it   */
+/*                     exactly); 0 for x >= t_s_len[b]                       */
+/*   frame_token[b][y] (or NULL) the token of frame y; -1 for y >=           */
+/*                     t_t_len[b]                                            */
+/* A row with t_t_len[b] == 0, t_s_len[b] == 0 or t_t_len[b] < t_s_len[b]    */
+/* has no alignment: durations 0, scores 0 and tokens -1 over the whole row. */
+/* Lengths are clamped to [0, t_t] / [0, t_s].  Returns VITS_E_ARG for a     */
+/* null neg_cent / length / durations pointer, a non-positive size or a      */
+/* workspace of fewer than vits_maximum_path_workspace bytes, VITS_E_UNSUP   */
+/* for t_s beyond the widest kernel (2048).                                  */
+int vits_maximum_path_durations(const float* neg_cent, const int32_t* t_t_len,
+                                const int32_t* t_s_len, int32_t* durations, float* scores,
+                                int32_t* frame_token, int batch, int t_t, int t_s,
+                                void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------- */
 /* MAS scores (models.py:483-490): neg_cent[b][y][x] = sum_d(-0.5 log 2pi */

@@ -360,6 +360,11 @@ _SIGS = {
          C.c_void_p, C.c_int64, C.c_void_p],
     ),
     "vits_maximum_path_workspace": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "vits_maximum_path_durations": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+         C.c_int, C.c_void_p, C.c_int64, C.c_void_p],
+    ),
     "vits_stft_mag_forward_multi": (C.c_int, [C.POINTER(StftJob), C.c_int, C.c_void_p]),
     "vits_stft_mag_backward_multi": (
         C.c_int, [C.POINTER(StftJob), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -30,7 +30,10 @@
 //    decision word of column index - l (the path moves at most one column
 //    per row), and each row is a readlane + bit test - no memory latency
 //    per row;
-//  * the path is written in one coalesced pass from the per-row column index.
+//  * the path is written in one coalesced pass from the per-row column index;
+//  * or (DUR, vits_maximum_path_durations) no path is written at all: the
+//    per-row column index becomes per-token durations, per-token score sums
+//    and the per-frame token, a few KB instead of the [t_t][t_s] tile.
 // (Round 5: per-row ballots + a one-lane backtrack, 194 us at B=64, 500 x 100.)
 #include "common.h"
 
@@ -95,13 +98,20 @@ __global__ __launch_bounds__(64) void mas_lengths_kernel(const void* mask, int d
   }
 }
 
-template <int XPL, bool BITS_LDS>
+// what the DUR epilogue writes (vits_maximum_path_durations)
+struct MasDurOut {
+  int32_t* durations;    // [B][T_s]
+  float* scores;         // [B][T_s] or null
+  int32_t* frame_token;  // [B][T_t] or null
+};
+
+template <int XPL, bool BITS_LDS, bool DUR>
 __global__ __launch_bounds__(256) void mas_kernel(const float* __restrict__ neg_cent,
                                                   const int32_t* __restrict__ tt_len,
                                                   const int32_t* __restrict__ ts_len, void* path,
                                                   int path_dt, int T_t, int T_s,
                                                   uint32_t* __restrict__ bits_global,
-                                                  int bits_in_lds) {
+                                                  int bits_in_lds, MasDurOut dur) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
@@ -126,6 +136,12 @@ __global__ __launch_bounds__(256) void mas_kernel(const float* __restrict__ neg_
   int t_s = ts_len[b];
   t_t = t_t < 0 ? 0 : (t_t > T_t ? T_t : t_t);
   t_s = t_s < 0 ? 0 : (t_s > T_s ? T_s : t_s);
+  // DUR: a row with no alignment (an empty side, or fewer frames than
+  // tokens) runs no DP and no backtrack; its outputs are defined below
+  const bool aligned = t_t > 0 && t_s > 0 && t_t >= t_s;
+  if constexpr (DUR) {
+    if (!aligned) t_t = 0;
+  }
 
   const float* nc = neg_cent + (int64_t)b * T_t * T_s;
   const int nchunks = (t_t + R - 1) / R;
@@ -261,13 +277,61 @@ __global__ __launch_bounds__(256) void mas_kernel(const float* __restrict__ neg_
   }
   __syncthreads();
 
-  // ---- write the full path tile ---------------------------------------------
-  // one wave per row, lanes along the row: coalesced, no index division
-  const int64_t pbase = (int64_t)b * T_t * T_s;
-  for (int y = wid; y < T_t; y += 4) {
-    const int sel = (y < t_t && t_s > 0) ? idx_row[y] : -1;
-    const int64_t rbase = pbase + (int64_t)y * T_s;
-    for (int x = lane; x < T_s; x += 64) store_dt(path, path_dt, rbase + x, x == sel ? 1.f : 0.f);
+  if constexpr (DUR) {
+    // ---- durations epilogue -------------------------------------------------
+    // the path column moves by 0 or 1 per frame, from 0 to t_s - 1: token x
+    // starts at the one frame where the column becomes x, and its duration is
+    // the difference of two starts.  The ring is free after the DP: it holds
+    // the starts [W + 1], the running score sums [W] and a window of the
+    // path's own scores val[y] = neg_cent[y][column of y].
+    int32_t* start = reinterpret_cast<int32_t*>(ring);
+    float* sums = ring + (W + 1);
+    float* val = ring + (2 * W + 1);
+    const int cap = 2 * R * W - (2 * W + 1);  // frames per window (>= 2 W)
+    if (aligned) {
+      for (int y = tid; y < t_t; y += 256) {
+        const int x = idx_row[y];
+        if (y == 0 || idx_row[y - 1] != x) start[x] = y;
+      }
+      if (tid == 0) start[t_s] = t_t;
+    }
+    for (int x = tid; x < W; x += 256) sums[x] = 0.f;
+    __syncthreads();
+    const int64_t obase = (int64_t)b * T_s;
+    for (int x = tid; x < T_s; x += 256)
+      dur.durations[obase + x] = (aligned && x < t_s) ? start[x + 1] - start[x] : 0;
+    if (dur.frame_token) {
+      const int64_t fbase = (int64_t)b * T_t;
+      for (int y = tid; y < T_t; y += 256) dur.frame_token[fbase + y] = y < t_t ? idx_row[y] : -1;
+    }
+    if (dur.scores) {
+      // token sums in increasing y, plain fp32 adds: the frames' scores are
+      // gathered by all threads (independent loads), then each token's
+      // thread adds its own run from LDS
+      for (int c0 = 0; c0 < t_t; c0 += cap) {
+        const int c1 = min(t_t, c0 + cap);
+        for (int y = c0 + tid; y < c1; y += 256) val[y - c0] = nc[(int64_t)y * T_s + idx_row[y]];
+        __syncthreads();
+        for (int x = tid; x < t_s; x += 256) {
+          const int y0 = max(start[x], c0), y1 = min(start[x + 1], c1);
+          float acc = sums[x];
+          for (int y = y0; y < y1; ++y) acc = __fadd_rn(acc, val[y - c0]);
+          sums[x] = acc;
+        }
+        __syncthreads();
+      }
+      for (int x = tid; x < T_s; x += 256) dur.scores[obase + x] = x < t_s ? sums[x] : 0.f;
+    }
+  } else {
+    // ---- write the full path tile -------------------------------------------
+    // one wave per row, lanes along the row: coalesced, no index division
+    const int64_t pbase = (int64_t)b * T_t * T_s;
+    for (int y = wid; y < T_t; y += 4) {
+      const int sel = (y < t_t && t_s > 0) ? idx_row[y] : -1;
+      const int64_t rbase = pbase + (int64_t)y * T_s;
+      for (int x = lane; x < T_s; x += 64)
+        store_dt(path, path_dt, rbase + x, x == sel ? 1.f : 0.f);
+    }
   }
 }
 
@@ -282,8 +346,10 @@ size_t bits_bytes(int t_t, int xpl) {
   return (size_t)((t_t + 31) / 32) * 64 * xpl * sizeof(uint32_t);
 }
 
+// dur: null = the path entries; else the durations entry (path unused)
 int mas_run(const float* neg_cent, const int32_t* tt, const int32_t* ts, void* path, int path_dt,
-            int batch, int T_t, int T_s, void* workspace, int64_t ws_bytes, hipStream_t s) {
+            int batch, int T_t, int T_s, void* workspace, int64_t ws_bytes, hipStream_t s,
+            const MasDurOut* dur = nullptr) {
   const int xpl = pick_xpl(T_s);
   if (xpl > 32) return VITS_E_UNSUP;
   const size_t ring = sizeof(float) * 2 * mas_rows(xpl) * 64 * xpl;
@@ -300,14 +366,23 @@ int mas_run(const float* neg_cent, const int32_t* tt, const int32_t* ts, void* p
   lds += sizeof(float) * 3 * 64 * xpl;
   if (lds > 160 * 1024) return VITS_E_UNSUP;
   dim3 grid(batch), block(256);
-#define MAS_CASE(X)                                                                         \
-  case X:                                                                                   \
-    if (in_lds)                                                                             \
-      hipLaunchKernelGGL((mas_kernel<X, true>), grid, block, lds, s, neg_cent, tt, ts, path, \
-                         path_dt, T_t, T_s, gbits, in_lds);                                 \
-    else                                                                                    \
-      hipLaunchKernelGGL((mas_kernel<X, false>), grid, block, lds, s, neg_cent, tt, ts, path, \
-                         path_dt, T_t, T_s, gbits, in_lds);                                 \
+  const MasDurOut none = {nullptr, nullptr, nullptr};
+#define MAS_LAUNCH(X, L, D)                                                                    \
+  hipLaunchKernelGGL((mas_kernel<X, L, D>), grid, block, lds, s, neg_cent, tt, ts, path, path_dt, \
+                     T_t, T_s, gbits, in_lds, D ? *dur : none)
+#define MAS_CASE(X)                   \
+  case X:                             \
+    if (dur) {                        \
+      if (in_lds)                     \
+        MAS_LAUNCH(X, true, true);    \
+      else                            \
+        MAS_LAUNCH(X, false, true);   \
+    } else {                          \
+      if (in_lds)                     \
+        MAS_LAUNCH(X, true, false);   \
+      else                            \
+        MAS_LAUNCH(X, false, false);  \
+    }                                 \
     break;
   switch (xpl) {
     MAS_CASE(1)
@@ -320,6 +395,7 @@ int mas_run(const float* neg_cent, const int32_t* tt, const int32_t* ts, void* p
       return VITS_E_UNSUP;
   }
 #undef MAS_CASE
+#undef MAS_LAUNCH
   return vits_launch_status();
 }
 
@@ -344,6 +420,19 @@ extern "C" int vits_maximum_path_lengths(const float* neg_cent, const int32_t* t
   VITS_CHECK_ARG(path_dtype >= 0 && path_dtype <= 3);
   return mas_run(neg_cent, t_t_len, t_s_len, path, path_dtype, batch, t_t, t_s, workspace,
                  workspace_bytes, as_stream(stream));
+}
+
+extern "C" int vits_maximum_path_durations(const float* neg_cent, const int32_t* t_t_len,
+                                           const int32_t* t_s_len, int32_t* durations,
+                                           float* scores, int32_t* frame_token, int batch,
+                                           int t_t, int t_s, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+  VITS_CHECK_ARG(neg_cent && t_t_len && t_s_len && durations && batch > 0 && t_t > 0 && t_s > 0);
+  if (pick_xpl(t_s) > 32) return VITS_E_UNSUP;
+  VITS_CHECK_ARG(workspace && workspace_bytes >= vits_maximum_path_workspace(batch, t_t, t_s));
+  const MasDurOut dur = {durations, scores, frame_token};
+  return mas_run(neg_cent, t_t_len, t_s_len, nullptr, VITS_DT_F32, batch, t_t, t_s, workspace,
+                 workspace_bytes, as_stream(stream), &dur);
 }
 
 extern "C" int vits_maximum_path(const float* neg_cent, const void* mask, int mask_dtype,

@@ -780,6 +780,115 @@ class EmoVITS(object):
         pcm = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int16)
         return pcm, np.asarray(offsets, dtype=np.int64), n_model
 
+    # -- forced alignment: recording and text in, durations out ---------------------
+    # the widest text the alignment kernel takes (vits_maximum_path_durations)
+    ALIGN_MAX_TOKENS = 2048
+
+    def _align_rows(self, wavs, spkids, texts, emos, sampling_rate_in, noise_scale):
+        """1 .. MAX_BATCH (recording, text) pairs through one alignment graph,
+        cached in self._graphs under ("align", batch bucket, text bucket,
+        frame bucket) (graph=False: the same align_bucketed call, eagerly).
+        Returns [(durations int32 [Tx], scores fp32 [Tx], frames)] on the host
+        after ONE device-to-host copy.  The host knows every length: a
+        recording with fewer frames than tokens is refused here."""
+        if self.device.type != "cuda":
+            raise ops._lib.VitsAmdError("EmoVITS.align: the vits_amd inference path runs on a "
+                                        f"ROCm GPU only (got {self.device})")
+        stft = self._vc_stft()
+        hop = stft[1]
+        n = len(wavs)
+        tokens = [int(np.shape(t)[0]) for t in texts]
+        for w, t in zip(wavs, tokens):
+            frames = self._vc_plan(np.asarray(w).reshape(-1).shape[0], sampling_rate_in)[2]
+            if t < 1 or frames < t:
+                raise ValueError(f"recording of {frames} frames cannot be aligned with {t} "
+                                 "tokens: every token takes at least one frame")
+        xb = -(-max(tokens) // self.TX_BUCKET) * self.TX_BUCKET
+        if xb > self.ALIGN_MAX_TOKENS:
+            raise ValueError(f"text of {max(tokens)} tokens exceeds the alignment kernel's "
+                             f"{self.ALIGN_MAX_TOKENS}")
+        rows = [self._vc_input(w, sampling_rate_in) for w in wavs]
+        frames = [f for _, f, _ in rows]
+        tyb = max(b for _, _, b in rows)
+        bb = 1 if n == 1 else self._batch_bucket(n)
+        resolved = [self._resolve(s, e) for s, e in zip(spkids, emos)]
+        sids = [int(s) for s, _ in resolved]
+        emo = torch.cat([e for _, e in resolved])
+        lens = [r.numel() for r, _, _ in rows]
+        wav = torch.zeros(n, max(lens), device=self.device)
+        for i, (r, _, _) in enumerate(rows):
+            wav[i, :lens[i]] = r
+        x = np.zeros((n, max(tokens), np.shape(texts[0])[1]), dtype=np.float32)
+        for i, t in enumerate(texts):
+            x[i, :tokens[i]] = t
+        x = torch.from_numpy(x).half().to(self.device)
+        noise = None
+        if noise_scale > 0:
+            if self._vc_gen is None:
+                self._vc_gen = torch.Generator(device=self.device)
+            noise = torch.randn(n, self.inter_channels, tyb, device=self.device,
+                                generator=self._vc_gen) * float(noise_scale)
+        if self.graph:
+            key = ("align", bb, xb, tyb)
+            run = self._graphs.pop(key, None)
+            if run is None:
+                while len(self._graphs) >= self.max_graphs:
+                    self._graphs.pop(next(iter(self._graphs)))
+                run = self.model.capture_align_bucketed(xb, tyb, batch=bb, stft=stft)
+            self._graphs[key] = run  # most recently used last
+            dur, scores, _ = run(wav, lens, x, tokens, emo, sids, noise)
+        else:
+            dev = self.device
+            ws = torch.zeros(bb, tyb * hop + hop - 1, device=dev)
+            ws[:n, :wav.shape[1]] = wav
+            xs = torch.zeros(bb, xb, x.shape[2], device=dev, dtype=x.dtype)
+            xs[:n, :x.shape[1]] = x
+            es = torch.zeros(bb, emo.shape[1], device=dev, dtype=emo.dtype)
+            es[:n] = emo
+            pad = [0] * (bb - n)
+            nz = None
+            if noise is not None:
+                nz = torch.zeros(bb, self.inter_channels, tyb, device=dev)
+                nz[:n] = noise
+            dur, scores, _ = self.model.align_bucketed(
+                ws, torch.tensor(lens + pad, dtype=torch.int32).to(dev), xs,
+                torch.tensor(tokens + pad, dtype=torch.int32).to(dev), es,
+                torch.tensor(sids + pad, dtype=torch.long).to(dev), nz, xb, tyb, stft=stft)
+        host = self._to_host(torch.cat([dur[:n], scores[:n].view(torch.int32)], 1)).reshape(n, -1)
+        return [(host[i, :tokens[i]].copy(), host[i, xb:xb + tokens[i]].view(np.float32).copy(),
+                 frames[i]) for i in range(n)]
+
+    def align(self, wav, spkid, text, emo, *, sampling_rate_in=None, noise_scale=0.0):
+        """Forced alignment of the recording ``wav`` (as ``convert`` takes
+        it: int16 or float, at ``sampling_rate_in``, default the model's
+        rate) with its text [Tx, c] spoken by spkid with emotion ``emo`` (as
+        ``infer`` takes them): (durations int32 [Tx], frames per token, each
+        at least 1, summing to ``frames``; scores float32 [Tx], the model's
+        log-likelihood of each token's frames (compare score / duration
+        between tokens: a low one marks text that does not match its audio);
+        frames = samples at the model's rate // hop).  One replay of a cached
+        graph and one device-to-host copy per call; noise_scale > 0 samples
+        the posterior, 0 (the default) takes its mean.  Raises ValueError for
+        a recording of more than 4096 frames, of at most (n_fft - hop) / 2
+        samples or of fewer frames than tokens, and for more than 2048
+        tokens; VitsAmdError on a CPU device."""
+        return self._align_rows([wav], [spkid], [text], [emo], sampling_rate_in, noise_scale)[0]
+
+    def align_batch(self, items, *, sampling_rate_in=None, noise_scale=0.0):
+        """align for items = [(wav, spkid, text, emo), ...]: the list of
+        align's results, equal to the loop over align (at noise_scale 0; a
+        draw's shape follows the batch).  A group of up to MAX_BATCH items
+        (batch buckets 2, 4, 8, 16) is one graph replay and one
+        device-to-host copy."""
+        items = list(items)
+        out = []
+        for lo, hi in self._groups(len(items)):
+            group = items[lo:hi]
+            out += self._align_rows([w for w, _, _, _ in group], [s for _, s, _, _ in group],
+                                    [t for _, _, t, _ in group], [e for _, _, _, e in group],
+                                    sampling_rate_in, noise_scale)
+        return out
+
     # text tokens are padded to a multiple of TX_BUCKET (masked encoder);
     # frame buckets are powers of two from 256 up to the noise buffer's 4096
     TX_BUCKET = 32

@@ -729,21 +729,44 @@ class SynthesizerTrn(nn.Module):
         run.pool_len = P
         return run
 
+    # ----------------------------------- the audio side of VC and alignment
+    def _audio_latents(self, spec, noise, lens, g, keep=False):
+        """spec [B, F, T] fp32 -> z = enc_q(spec) (noise None: the posterior
+        mean) -> z_p = flow(z; g), the forward flow, every layer masked at
+        lens (int32 [B], device); kernels only, no host sync.  Returns (z,
+        z_p, stage lengths int32 [n, B]); z_p is z updated in place unless
+        ``keep``."""
+        z, sl = engine.get_plan(self.enc_q, engine.PosteriorPlan).run_bucketed(
+            spec, noise, lens, stage_mult=self._stage_mult())
+        z_p = z.clone() if keep else z
+        engine.get_plan(self.flow, engine.CouplingFlowPlan).run_(z_p, g, lengths=sl[0],
+                                                                 forward=True)
+        return z, z_p, sl
+
+    def _spec_rows(self, what, wav, n_samples, t_y, stft):
+        """The linear spectrogram of a ragged waveform batch over a bucket of
+        t_y frames (convert_bucketed documents it): (spec [B, F, t_y], y_len
+        int32 [B])."""
+        n_fft, hop, win = (int(v) for v in stft)
+        if hop != self.hop_total or n_fft // 2 + 1 != self.enc_q.in_channels:
+            raise ValueError(f"{what}: stft {tuple(stft)} does not fit a model of "
+                             f"{self.enc_q.in_channels} bins and hop {self.hop_total}")
+        if wav.dim() != 2 or wav.dtype != torch.float32 or wav.shape[1] < t_y * hop:
+            raise ValueError(f"{what}: wav must be fp32 [B, >= {t_y * hop}], got "
+                             f"{wav.dtype} {tuple(wav.shape)}")
+        return engine.ops.stft_mag_rows(wav, n_samples, self._vc_window(win, wav.device), n_fft,
+                                        hop, win, t_y, pad=(n_fft - hop) // 2, eps=1e-6)
+
     # ------------------------------------------------------- voice conversion
     def _vc_core(self, spec, noise, lens, sid_src, sid_tgt, keep=False):
         """spec [B, F, T] fp32 -> enc_q -> flow(g_src) -> flow^-1(g_tgt) ->
         dec(g_tgt), every layer masked at lens (int32 [B], device); kernels
         and the two embedding lookups only, no host sync.  Returns (o fp32
         [B, 1, T * hop], (z, z_p, z_hat) when ``keep`` else None)."""
-        g_src = engine._f32(self.emb_g(sid_src))
         g_tgt = engine._f32(self.emb_g(sid_tgt))
-        z, sl = engine.get_plan(self.enc_q, engine.PosteriorPlan).run_bucketed(
-            spec, noise, lens, stage_mult=self._stage_mult())
-        fplan = engine.get_plan(self.flow, engine.CouplingFlowPlan)
-        z_p = z.clone() if keep else z
-        fplan.run_(z_p, g_src, lengths=sl[0], forward=True)
+        z, z_p, sl = self._audio_latents(spec, noise, lens, engine._f32(self.emb_g(sid_src)), keep)
         z_hat = z_p.clone() if keep else z_p
-        fplan.run_(z_hat, g_tgt, lengths=sl[0])
+        engine.get_plan(self.flow, engine.CouplingFlowPlan).run_(z_hat, g_tgt, lengths=sl[0])
         o = engine.get_plan(self.dec, engine.GeneratorPlan).run(z_hat, g_tgt, lengths=sl[1:])
         # the decoder's last conv runs unmasked over the whole buffer (its halo
         # spills 3 samples past a row's end, and skipped tiles hold nothing
@@ -798,18 +821,7 @@ class SynthesizerTrn(nn.Module):
         y_len * hop samples of row b are bit for bit voice_conversion of that
         row alone on its own exact-length spectrogram; the rest is zero."""
         engine._check_gpu(wav, "SynthesizerTrn.convert_bucketed")
-        n_fft, hop, win = (int(v) for v in stft)
-        if hop != self.hop_total or n_fft // 2 + 1 != self.enc_q.in_channels:
-            raise ValueError(f"convert_bucketed: stft {tuple(stft)} does not fit a model of "
-                             f"{self.enc_q.in_channels} bins and hop {self.hop_total}")
-        B, cap = wav.shape
-        t_y = int(t_y)
-        if wav.dtype != torch.float32 or cap < t_y * hop:
-            raise ValueError(f"convert_bucketed: wav must be fp32 [B, >= {t_y * hop}], got "
-                             f"{wav.dtype} {tuple(wav.shape)}")
-        spec, y_len = engine.ops.stft_mag_rows(wav, n_samples, self._vc_window(win, wav.device),
-                                               n_fft, hop, win, t_y, pad=(n_fft - hop) // 2,
-                                               eps=1e-6)
+        spec, y_len = self._spec_rows("convert_bucketed", wav, n_samples, int(t_y), stft)
         with engine.ops.length_skip(64):
             o, _ = self._vc_core(spec, noise, y_len, sid_src, sid_tgt)
         return o, y_len
@@ -839,21 +851,8 @@ class SynthesizerTrn(nn.Module):
             return self.convert_bucketed(static["wav"], static["n"], static["src"], static["tgt"],
                                          static["noise"], t_y, stft=(n_fft, hop, win))
 
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                body()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = body()
-
-        def _ints(v, n, dtype):
-            t = torch.as_tensor(v, dtype=dtype).reshape(-1)[:n]
-            if t.numel() != n:
-                raise ValueError(f"convert replay: {n} rows need {n} values, got {t.numel()}")
-            return t
+        graph, out = self._capture_body(body, warmup, dev)
+        _ints = self._row_ints
 
         def run(wav, n_samples, sid_src, sid_tgt, noise=None):
             n = wav.shape[0]
@@ -876,6 +875,154 @@ class SynthesizerTrn(nn.Module):
 
         run.graph = graph
         run.static = static
+        run.t_y = t_y
+        run.batch = batch
+        return run
+
+    @staticmethod
+    def _capture_body(body, warmup, dev):
+        """Warm ``body`` up on a side stream, then capture it: (graph, its outputs)."""
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                body()
+        torch.cuda.current_stream(dev).wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = body()
+        return graph, out
+
+    @staticmethod
+    def _row_ints(v, n, dtype):
+        t = torch.as_tensor(v, dtype=dtype).reshape(-1)[:n]
+        if t.numel() != n:
+            raise ValueError(f"replay: {n} rows need {n} values, got {t.numel()}")
+        return t
+
+    # ------------------------------------------------------ forced alignment
+    def _align_core(self, spec, noise, y_len, x, x_len, emo, sid):
+        """Both sides of the model scored against each other and the best
+        monotonic path reduced to durations: (durations int32 [B, Tx], scores
+        fp32 [B, Tx], (z_p, m_p, logs_p, neg_cent) in fp32).  The text side is
+        TextEncoder.infer of each row's own tokens (pad_exact), the audio side
+        voice conversion's (_audio_latents) with the row's speaker; kernels
+        and one embedding lookup only, no host sync."""
+        g = self.emb_g(sid)
+        _, m_p, logs_p = self.enc_p.forward_masked_hip(x, x_len, emo, g, pad_exact=True)
+        _, z_p, _ = self._audio_latents(spec, noise, y_len, engine._f32(g))
+        nc = engine.ops.neg_cent(z_p, m_p, logs_p)
+        dur, scores, _ = engine.ops.maximum_path_durations(nc, y_len, x_len)
+        return dur, scores, (z_p, m_p, logs_p, nc)
+
+    @torch.no_grad()
+    def align(self, x, x_lengths, y, y_lengths, emo, sid, noise=None):
+        """Forced alignment of the linear spectrogram y [B, F, Ty] (y_lengths
+        frames) with the text x [B, Tx, c] (x_lengths tokens) of speaker sid:
+        the monotonic path that the training forward searches (models.py:
+        483-498), without alignment noise, autograd or decoder.  m_p, logs_p
+        = enc_p(x), z = enc_q(y) (``noise`` [B, C, Ty], already scaled, is the
+        posterior draw; None, the default, takes the posterior mean), z_p =
+        flow(z; g), neg_cent = the four terms of models.py:484-489, then MAS.
+        Exact-length and eager: this is the definition align_bucketed is held
+        to.  Returns (durations int32 [B, Tx]: frames per token, 0 past
+        x_lengths; scores fp32 [B, Tx]: the sum of neg_cent over each token's
+        frames, a log-likelihood (higher = better match), 0 past x_lengths;
+        (z_p, m_p, logs_p, neg_cent) in fp32).  A row with no frames, no
+        tokens or fewer frames than tokens has no alignment: durations and
+        scores are 0."""
+        engine._check_gpu(x, "SynthesizerTrn.align")
+        dev = x.device
+        y_len = y_lengths.to(device=dev, dtype=torch.int32).contiguous()
+        x_len = x_lengths.to(device=dev, dtype=torch.int32).contiguous()
+        return self._align_core(engine._f32(y).contiguous(), noise, y_len, x, x_len, emo, sid)
+
+    @torch.no_grad()
+    def align_bucketed(self, wav, n_samples, x, x_lengths, emo, sid, noise, t_x, t_y, *, stft):
+        """align from the waveform with NO host synchronisation, over a
+        static bucket of t_x tokens and t_y frames (capture_align_bucketed
+        makes it one hipGraph).  wav [B, >= t_y * hop] fp32 and n_samples
+        int32 [B] as convert_bucketed takes them (``stft`` too; the
+        spectrogram is computed per row at its own length, y_len = n_samples
+        // hop); x [B, t_x, c] with x_lengths int32 [B] on the device; noise
+        [B, C, t_y] (pre-scaled) or None.  The audio side runs masked at
+        y_len under ops.length_skip(64), the text side masked at x_lengths.
+
+        Returns (durations int32 [B, t_x], scores fp32 [B, t_x], y_len int32
+        [B]): the first x_lengths[b] entries of row b are bit for bit
+        ``align`` of that row alone at its exact lengths; the rest is zero."""
+        engine._check_gpu(wav, "SynthesizerTrn.align_bucketed")
+        t_x, t_y = int(t_x), int(t_y)
+        if x.dim() != 3 or x.shape[0] != wav.shape[0] or x.shape[1] != t_x:
+            raise ValueError(f"align_bucketed: x must be [{wav.shape[0]}, {t_x}, c], got "
+                             f"{tuple(x.shape)}")
+        spec, y_len = self._spec_rows("align_bucketed", wav, n_samples, t_y, stft)
+        x_len = x_lengths.to(device=x.device, dtype=torch.int32).contiguous()
+        with engine.ops.length_skip(64):
+            dur, scores, _ = self._align_core(spec, noise, y_len, x, x_len, emo, sid)
+        return dur, scores, y_len
+
+    @torch.no_grad()
+    def capture_align_bucketed(self, t_x, t_y, batch=1, warmup=2, *, stft):
+        """One hipGraph for align_bucketed over [batch, t_x tokens, t_y
+        frames] (``stft`` as there).  Returns run(wav, n_samples, x,
+        x_lengths, emo, sid, noise=None) -> (durations [batch, t_x], scores
+        [batch, t_x], y_len [batch]), views of static buffers: wav [n, <= t_y
+        * hop + hop - 1] fp32 rows, x [n, <= t_x, c], emo [n, 1024], n_samples
+        / x_lengths / sid n host ints (or tensors), noise [n, C, t_y] or None
+        (the static noise is then zeroed: the posterior mean).  Rows at or
+        past n get zero text and length 0 on both sides: they come back as
+        "no alignment"."""
+        dev = next(self.parameters()).device
+        dt = next(self.parameters()).dtype
+        n_fft, hop, win = (int(v) for v in stft)
+        t_x, t_y, batch = int(t_x), int(t_y), int(batch)
+        cap = t_y * hop + hop - 1
+        static = dict(wav=torch.zeros(batch, cap, device=dev),
+                      n=torch.zeros(batch, device=dev, dtype=torch.int32),
+                      x=torch.zeros(batch, t_x, self.text_channels, device=dev, dtype=dt),
+                      xl=torch.zeros(batch, device=dev, dtype=torch.int32),
+                      emo=torch.zeros(batch, 1024, device=dev, dtype=dt),
+                      sid=torch.zeros(batch, device=dev, dtype=torch.long),
+                      noise=torch.zeros(batch, self.inter_channels, t_y, device=dev))
+        self._vc_window(win, dev)  # (built outside the capture)
+
+        def body():
+            return self.align_bucketed(static["wav"], static["n"], static["x"], static["xl"],
+                                       static["emo"], static["sid"], static["noise"], t_x, t_y,
+                                       stft=(n_fft, hop, win))
+
+        graph, out = self._capture_body(body, warmup, dev)
+        _ints = self._row_ints
+
+        def run(wav, n_samples, x, x_lengths, emo, sid, noise=None):
+            n = wav.shape[0]
+            if not 1 <= n <= batch or wav.shape[1] > cap:
+                raise ValueError(f"align replay: wav {tuple(wav.shape)} does not fit "
+                                 f"[{batch}, {cap}]")
+            if x.shape[0] != n or x.shape[1] > t_x:
+                raise ValueError(f"align replay: x {tuple(x.shape)} does not fit [{n}, {t_x}, c]")
+            static["wav"][:n, :wav.shape[1]].copy_(wav)
+            static["n"].zero_()
+            static["n"][:n].copy_(_ints(n_samples, n, torch.int32))
+            static["x"].zero_()
+            static["x"][:n, :x.shape[1]].copy_(x)
+            static["xl"].zero_()
+            static["xl"][:n].copy_(_ints(x_lengths, n, torch.int32))
+            static["emo"].zero_()
+            static["emo"][:n].copy_(emo)
+            static["sid"].zero_()
+            static["sid"][:n].copy_(_ints(sid, n, torch.long))
+            if noise is None:
+                static["noise"].zero_()
+            else:
+                static["noise"][:n].copy_(noise)
+            graph.replay()
+            return out
+
+        run.graph = graph
+        run.static = static
+        run.t_x = t_x
         run.t_y = t_y
         run.batch = batch
         return run

@@ -1389,6 +1389,40 @@ def maximum_path_lengths(neg_cent: torch.Tensor, t_t: torch.Tensor, t_s: torch.T
     return path
 
 
+def maximum_path_durations(neg_cent: torch.Tensor, t_t: torch.Tensor, t_s: torch.Tensor, *,
+                           scores: bool = True, frame_token: bool = False):
+    """Forced alignment of neg_cent [B, Tt, Ts] fp32 at per-row lengths t_t /
+    t_s (int32 [B], device): the DP and backtrack of maximum_path_lengths
+    with the path reduced in the kernel (vits_maximum_path_durations; no [B,
+    Tt, Ts] path is written).  Returns (durations int32 [B, Ts], scores fp32
+    [B, Ts] or None, frame_token int32 [B, Tt] or None): frames per token, the
+    sequential fp32 sum of the token's neg_cent entries, the token of every
+    frame (-1 past the row's frames).  A row with an empty side or fewer
+    frames than tokens has no alignment: durations 0, scores 0, tokens -1.
+    No host sync: capture-safe."""
+    require_device(neg_cent, t_t, t_s)
+    if neg_cent.dim() != 3:
+        raise _lib.VitsAmdError(f"maximum_path_durations: neg_cent {tuple(neg_cent.shape)}")
+    nc = neg_cent.detach().to(torch.float32).contiguous()
+    B, Tt, Ts = nc.shape
+    tt = t_t.to(torch.int32).contiguous()
+    ts = t_s.to(torch.int32).contiguous()
+    if tt.numel() != B or ts.numel() != B:
+        raise _lib.VitsAmdError(f"maximum_path_durations: {B} rows need {B} lengths, got "
+                                f"{tt.numel()} and {ts.numel()}")
+    dur = torch.empty(B, Ts, device=nc.device, dtype=torch.int32)
+    sc = torch.empty(B, Ts, device=nc.device, dtype=torch.float32) if scores else None
+    ft = torch.empty(B, Tt, device=nc.device, dtype=torch.int32) if frame_token else None
+    lib = _lib.load()
+    wsb = int(lib.vits_maximum_path_workspace(B, Tt, Ts))
+    ws = torch.empty(max(wsb, 16), device=nc.device, dtype=torch.uint8)
+    check(lib.vits_maximum_path_durations(nc.data_ptr(), tt.data_ptr(), ts.data_ptr(),
+                                          dur.data_ptr(), _ptr(sc), _ptr(ft), B, Tt, Ts,
+                                          ws.data_ptr(), ws.numel(), _stream_ptr(nc.device)),
+          "vits_maximum_path_durations")
+    return dur, sc, ft
+
+
 # ---------------------------------------------------------------------------
 # STFT magnitude with autograd
 # ---------------------------------------------------------------------------

@@ -229,6 +229,46 @@ class VITSWrap(object):
         return out
 
     @torch.no_grad()
+    def aligning(self, inputs: dict) -> dict:
+        """Forced-alignment request: {"wav" (int16 or float samples), "text",
+        "spkid", "emotion", "sampling_rate_in", "id"} -> the same dict plus
+        "durations" (int32 [Tx], frames per token of the front end's vector
+        sequence), "boundaries_s" (float64 [Tx + 1]: token i spans
+        boundaries_s[i] .. boundaries_s[i + 1] seconds of the recording at the
+        model's rate), "scores" (float32 [Tx]), "frames", "segtext", and the
+        timing fields of ``speaking`` (time_used_frontend / _backend in ms,
+        rtf against the recording's duration).  The text must be one segment:
+        text that _split_utt_text would cut is refused (ValueError), because
+        the recording cannot be cut to match before it is aligned.  Unlike
+        ``converting`` this needs no device_post: there is no output stage,
+        only durations come back; it needs a ROCm GPU (EmoVITS.align)."""
+        utt_id = inputs.setdefault("id", str(time.time()).replace(".", "_"))
+        spkid = int(inputs.get("spkid", self.default_spkid))
+        ids, texts = self._split_utt_text(utt_id, inputs.get("text", "。"))
+        if len(texts) != 1:
+            raise ValueError(f"aligning: the text splits into {len(texts)} segments of at most "
+                             f"{self.max_utt_length} characters; align one segment per recording")
+        t0 = time.time()
+        _, segtext, vec = self.textparser(ids[0], texts[0])
+        t1 = time.time()
+        durations, scores, frames = self.speecher.align(
+            inputs["wav"], spkid, vec, inputs.get("emotion"),
+            sampling_rate_in=inputs.get("sampling_rate_in"))
+        t_back = time.time() - t1
+        sp = self.speecher
+        out = inputs
+        out["durations"] = durations
+        out["boundaries_s"] = (np.concatenate([[0], np.cumsum(durations, dtype=np.int64)])
+                               * (sp.hop_size / sp.sampling_rate))
+        out["scores"] = scores
+        out["frames"] = frames
+        out["segtext"] = segtext.printer() if hasattr(segtext, "printer") else str(segtext)
+        out["time_used_frontend"] = (t1 - t0) * 1000
+        out["time_used_backend"] = t_back * 1000
+        out["rtf"] = (t1 - t0 + t_back) / max(1e-9, frames * sp.hop_size / sp.sampling_rate)
+        return out
+
+    @torch.no_grad()
     def speaking_many(self, list_of_inputs) -> list:
         """``speaking`` for several requests at once: one dict per input, the
         same ``wav``, ``sr`` and ``segment_info`` as ``[speaking(i) for i in
