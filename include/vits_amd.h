@@ -49,6 +49,12 @@
  *   vits_*_rows              the four above with the speed, the ratio, the
  *                            volume and the tail per row: requests with
  *                            different controls behind one graph replay
+ *   vits_duration_plan       per-token durations under a caller's controls
+ *                            (pins, per-token scales, a total to fit), the
+ *                            attn argument of infer_p2 (models.py:568) built
+ *                            on the device
+ *   vits_*_int               vits_expand_durations / vits_draw_starts from
+ *                            those integer durations
  */
 #ifndef VITS_AMD_H
 #define VITS_AMD_H
@@ -281,6 +287,67 @@ int vits_draw_starts_rows(const float* logw, int64_t logw_bstride, const int32_t
                           const float* rates, int half_round, int channels, int64_t noise_len,
                           const uint32_t* pool, int pool_n, const int32_t* n_rows, int batch,
                           int64_t* starts, int32_t* meta, void* stream);
+
+/* ---------------------------------------------------------------------- */
+/* Duration control.  vits_duration_plan turns the duration predictor's     */
+/* logw and a caller's controls into integer durations on the device (one   */
+/* 256-thread workgroup per row, no host sync, safe under stream capture):  */
+/*   given     int32 [batch][t_x] or NULL: >= 0 pins the token to exactly    */
+/*             that many frames (0 allowed), < 0 leaves it free              */
+/*   tok_scale fp32 [batch][t_x] or NULL: per-token factor (>= 0) on w       */
+/*   target    int32 [batch] or NULL: > 0 = the row must last exactly that   */
+/*             many frames, <= 0 = no target                                 */
+/*   rate / rates: the scalar speed, or fp32 [batch] per-row speeds when     */
+/*             rates != NULL (rate is then ignored)                          */
+/* A free token x < x_len[b] (x_len NULL: t_x) has w = exp(logw) * rate with */
+/* vits_expand_durations' fp16 roundings under half_round, then * tok_scale  */
+/* (one more fp16 rounding under half_round).  Without a target d = (int)    */
+/* ceil(w).  With a target T the rate is not applied (w = exp(logw) *        */
+/* tok_scale) and the free tokens F are fitted in integer arithmetic: P =    */
+/* the sum of the pins, E = T - P - |F|,                                     */
+/*   q[x] = max(llrint(min(max(w, 2^-8), 2^15) * 256) - 128, 1)   (int64)    */
+/*   Q[x] = inclusive prefix sum of q over F in token order, Qtot = the last */
+/*   B[x] = (Q[x] * E + Qtot / 2) / Qtot                    (int64 division) */
+/*   d[x] = 1 + B[x] - B[previous free token]             (B = 0 before F)   */
+/* so every free token gets >= 1 frame, pins are untouched and the row sums  */
+/* to exactly T, whatever the order of summation.  (A NaN w counts as 2^-8.) */
+/* Domain: a pin above 2^18 counts as 2^18 and ceil(w) is clamped to [0,     */
+/* 2^18] (an Inf or huge w saturates, a NaN or negative w gives 0 frames):   */
+/* the clamp of the _int entry points below, so `total` and their y_len      */
+/* always agree.                                                             */
+/* dur int32 [batch][t_x]: 0 at and past x_len.  meta int32 [2][batch]:      */
+/* total (the plain integer sum of the row: no fp16 rounding of the sum, no  */
+/* max(., 1)) and status: 1 when the target cannot   */
+/* be met (E < 0, or no free token and T != P, or T > 2^24, the range of     */
+/* the int64 fit): the row then gets the no-target durations; else 0.        */
+/* w_out fp32 [batch][t_x] or NULL: the w behind each free token's duration  */
+/* (rate applied unless the row was fitted), 0 for pinned and padded tokens. */
+/* VITS_E_ARG: NULL logw / dur / meta, batch <= 0, t_x <= 0; VITS_E_SHAPE:   */
+/* logw_bstride < t_x; VITS_E_UNSUP: t_x > 4096.                             */
+/* ---------------------------------------------------------------------- */
+int vits_duration_plan(const float* logw, int64_t logw_bstride, const int32_t* x_len, int t_x,
+                       float rate, const float* rates, int half_round, const int32_t* given,
+                       const float* tok_scale, const int32_t* target, int32_t* dur, int32_t* meta,
+                       float* w_out, int batch, void* stream);
+
+/* vits_expand_durations / vits_draw_starts reading integer durations dur    */
+/* int32 [batch] rows of dur_bstride (>= t_x) in place of logw / rate /      */
+/* half_round: token x < x_len[b] lasts min(max(dur[b][x], 0), 2^18) frames  */
+/* (0: the token gets no frame), y_len = max(sum, 1) as a plain integer sum. */
+/* Everything else (noise modes 0 / 1 / 2, stage_mult, n_rows, the -1 / -2   */
+/* statuses, zeros past y_len) is the logw entry points' rule, and with dur  */
+/* = ceil(exp(logw) * rate) they compute bit for bit what those compute      */
+/* (fp32 model; the half model's fp16 sum differs above 2048 frames).        */
+int vits_expand_durations_int(const int32_t* dur, int64_t dur_bstride, const int32_t* x_len,
+                              int t_x, const float* m, const float* s, int64_t ms_bstride,
+                              int32_t ms_cstride, const float* noise, int noise_mode,
+                              const int32_t* noise_start, int64_t noise_len, float noise_scale,
+                              float* z, int batch, int channels, int t_y, int32_t* lens,
+                              const int32_t* stage_mult, int n_stage, void* stream);
+int vits_draw_starts_int(const int32_t* dur, int64_t dur_bstride, const int32_t* x_len, int t_x,
+                         int channels, int64_t noise_len, const uint32_t* pool, int pool_n,
+                         const int32_t* n_rows, int batch, int64_t* starts, int32_t* meta,
+                         void* stream);
 
 int vits_conv_post_tanh(const float* x, int64_t x_bstride, int32_t x_cstride, const float* w,
                         float* y, int batch, int channels, int t_len, int ksize, void* stream);

@@ -526,6 +526,22 @@ _SIGS = {
         [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64,
          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     ),
+    "vits_duration_plan": (
+        C.c_int,
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    ),
+    "vits_expand_durations_int": (
+        C.c_int,
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+         C.c_int64, C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
+         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    ),
+    "vits_draw_starts_int": (
+        C.c_int,
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int64,
+         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
     "vits_resample_poly_rows": (
         C.c_int,
         [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.POINTER(PostRow),

@@ -13,6 +13,8 @@
 //                         host sync of infer() removed
 //   vits_draw_starts      the noise-slice starts of a batch (infer.py:173's
 //                         randint of consecutive calls) in one launch
+//   vits_duration_plan    durations under pins, per-token scales and a target
+//                         total; vits_*_int: the two above from int durations
 //   vits_conv_post_tanh  Generator tail, models.py:315-317
 #include "common.h"
 
@@ -150,18 +152,14 @@ struct EdStages {
   int n;
 };
 
-// The integer durations of one utterance and their inclusive scan, by a whole
-// 256-thread workgroup: cum[x] = sum_{x' <= x} ceil(exp(logw[x']) * rate) for
-// x < t_x (tokens at or past nx last 0 frames), `total` = cum[t_x - 1];
-// returns y_len = max(total, 1) (the half model's fp16 sum applied).  The
-// one place this arithmetic lives: expand_durations_kernel expands with it
-// and draw_starts_kernel sizes the noise slices with it, so the two cannot
-// disagree about a length.  Every thread of the workgroup must call it; cum
-// and part are valid for all threads on return (callers that reuse them
-// synchronise first).
-__device__ __forceinline__ int ed_scan_durations(const float* __restrict__ logw_row, int nx,
-                                                 int t_x, float rate, int half_round, int* cum,
-                                                 int* part, int& total) {
+// The inclusive scan of one utterance's integer durations, by a whole
+// 256-thread workgroup: cum[x] = sum_{x' <= x} dur_of(x') for x < t_x; returns
+// cum[t_x - 1].  Every thread of the workgroup must call it; cum and part are
+// valid for all threads on return (callers that reuse them synchronise
+// first).  The one scan under the logw forms (ed_scan_durations) and the
+// int32 forms (ed_scan_given) of the expansion and the start draw.
+template <typename DurFn>
+__device__ __forceinline__ int ed_scan_tokens(int t_x, int* cum, int* part, DurFn dur_of) {
   const int tid = threadIdx.x;
   // integer durations of this thread's consecutive tokens, block scan
   const int per = (t_x + 255) / 256;
@@ -170,15 +168,7 @@ __device__ __forceinline__ int ed_scan_durations(const float* __restrict__ logw_
   for (int i = 0; i < per; ++i) {
     const int x = xb0 + i;
     if (x < t_x) {
-      int d = 0;
-      if (x < nx) {
-        float w = expf(logw_row[x]);
-        if (half_round) w = (float)(_Float16)w;  // the fp16 model's torch.exp
-        w = w * rate;
-        if (half_round) w = (float)(_Float16)w;
-        d = (int)ceilf(w);
-      }
-      local += d;
+      local += dur_of(x);
       cum[x] = local;  // inclusive within the thread for now
     }
   }
@@ -196,12 +186,72 @@ __device__ __forceinline__ int ed_scan_durations(const float* __restrict__ logw_
     if (x < t_x) cum[x] += base;
   }
   __syncthreads();
+  return part[255];
+}
+
+// w of one token: exp(logw) * rate with the fp16 roundings of the half model
+// (its torch.exp, then its multiply).  The one place this arithmetic lives:
+// the expansion, the start draw and the duration plan all call it.
+__device__ __forceinline__ float ed_token_w(float logw, float rate, int half_round) {
+  float w = expf(logw);
+  if (half_round) w = (float)(_Float16)w;  // the fp16 model's torch.exp
+  w = w * rate;
+  if (half_round) w = (float)(_Float16)w;
+  return w;
+}
+
+// The integer durations of one utterance from the duration predictor:
+// cum[x] = sum_{x' <= x} ceil(exp(logw[x']) * rate) for x < t_x (tokens at or
+// past nx last 0 frames), `total` = cum[t_x - 1]; returns y_len = max(total,
+// 1) (the half model's fp16 sum applied).  expand_durations_kernel expands
+// with it and draw_starts_kernel sizes the noise slices with it, so the two
+// cannot disagree about a length.
+__device__ __forceinline__ int ed_scan_durations(const float* __restrict__ logw_row, int nx,
+                                                 int t_x, float rate, int half_round, int* cum,
+                                                 int* part, int& total) {
+  total = ed_scan_tokens(t_x, cum, part, [&](int x) {
+    return x < nx ? (int)ceilf(ed_token_w(logw_row[x], rate, half_round)) : 0;
+  });
   // y_len = clamp_min(sum(w_ceil), 1): the half model sums in fp16 (its
   // torch.sum result rounds to half: totals > 2048 frames round to even)
-  int y_len = part[255];
+  int y_len = total;
   if (half_round) y_len = (int)(float)(_Float16)(float)y_len;
-  total = part[255];
   return max(y_len, 1);
+}
+
+// The same from given integer durations (vits_duration_plan's `dur`, or a
+// caller's): token x < nx lasts dur_row[x] frames, clamped to [0,
+// ED_MAX_DUR] so that 4096 tokens cannot overflow the int scan; y_len =
+// max(total, 1), a plain integer sum (no fp16 rounding: the durations are
+// the caller's integers, not a half model's sum).
+constexpr int ED_MAX_DUR = 1 << 18;
+__device__ __forceinline__ int ed_scan_given(const int32_t* __restrict__ dur_row, int nx, int t_x,
+                                             int* cum, int* part, int& total) {
+  total = ed_scan_tokens(t_x, cum, part, [&](int x) {
+    return x < nx ? min(max(dur_row[x], 0), ED_MAX_DUR) : 0;
+  });
+  return max(total, 1);
+}
+
+// Durations source of the expansion / start-draw kernels: the predictor's
+// logw (rate, half_round) or int32 durations.
+struct EdSrc {
+  const float* logw;      // [B] rows of logw_bstride (kInt = false)
+  const int32_t* dur;     // [B] rows of bstride      (kInt = true)
+  int64_t bstride;
+  float rate;
+  const float* rates;
+  int half_round;
+};
+template <bool kInt>
+__device__ __forceinline__ int ed_scan_src(const EdSrc& src, int b, int nx, int t_x, int* cum,
+                                           int* part, int& total) {
+  if constexpr (kInt)
+    return ed_scan_given(src.dur + (int64_t)b * src.bstride, nx, t_x, cum, part, total);
+  else
+    return ed_scan_durations(src.logw + (int64_t)b * src.bstride, nx, t_x,
+                             src.rates ? src.rates[b] : src.rate, src.half_round, cum, part,
+                             total);
 }
 
 // numpy's legacy RandomState.randint(high) for high - 1 = rng in [1, 2^32):
@@ -224,9 +274,9 @@ __device__ __forceinline__ int ed_masked_draw(const uint32_t* __restrict__ pool,
   return -2;
 }
 
+template <bool kInt>
 __global__ __launch_bounds__(256) void expand_durations_kernel(
-    const float* __restrict__ logw, int64_t logw_bstride, const int32_t* __restrict__ x_len,
-    int t_x, float rate, const float* __restrict__ rates, int half_round,
+    const EdSrc src, const int32_t* __restrict__ x_len, int t_x,
     const float* __restrict__ m, const float* __restrict__ s, int64_t ms_bstride, int ms_cstride,
     const float* __restrict__ noise, int noise_mode, const int32_t* __restrict__ noise_start,
     int64_t noise_len, float noise_scale, float* __restrict__ z, int channels, int t_y, int batch, int32_t* __restrict__ lens,
@@ -239,8 +289,7 @@ __global__ __launch_bounds__(256) void expand_durations_kernel(
   const int nx = x_len ? min(x_len[b], t_x) : t_x;
   // 1) integer durations, their scan and y_len
   int total;
-  const int y_len = ed_scan_durations(logw + (int64_t)b * logw_bstride, nx, t_x,
-                                      rates ? rates[b] : rate, half_round, cum, part, total);
+  const int y_len = ed_scan_src<kInt>(src, b, nx, t_x, cum, part, total);
   if (blockIdx.x == 0 && tid < st.n) lens[tid * batch + b] = y_len * st.mult[tid];
   // 2) token of each frame of this workgroup: first x with cum[x] > t
   const int t0 = blockIdx.x * ED_T;
@@ -330,9 +379,9 @@ __global__ __launch_bounds__(256) void expand_durations_kernel(
 // or past *n_rows (the padding of a batch bucket) draw nothing: status 0,
 // start 0.  meta = [y_len (batch) | status (batch) | used_total].
 // ---------------------------------------------------------------------------
+template <bool kInt>
 __global__ __launch_bounds__(256) void draw_starts_kernel(
-    const float* __restrict__ logw, int64_t logw_bstride, const int32_t* __restrict__ x_len,
-    int t_x, float rate, const float* __restrict__ rates, int half_round, int channels,
+    const EdSrc src, const int32_t* __restrict__ x_len, int t_x, int channels,
     int64_t noise_len, const uint32_t* __restrict__ pool, int pool_n,
     const int32_t* __restrict__ n_rows_p, int batch, int64_t* __restrict__ starts,
     int32_t* __restrict__ meta) {
@@ -343,8 +392,7 @@ __global__ __launch_bounds__(256) void draw_starts_kernel(
   for (int b = 0; b < batch; ++b) {
     const int nx = x_len ? min(x_len[b], t_x) : t_x;
     int total;
-    const int y_len = ed_scan_durations(logw + (int64_t)b * logw_bstride, nx, t_x,
-                                        rates ? rates[b] : rate, half_round, cum, part, total);
+    const int y_len = ed_scan_src<kInt>(src, b, nx, t_x, cum, part, total);
     __syncthreads();  // cum / part are rewritten for the next row
     if (threadIdx.x == 0) {
       int64_t start = 0;
@@ -367,6 +415,162 @@ __global__ __launch_bounds__(256) void draw_starts_kernel(
     }
   }
   if (threadIdx.x == 0) meta[2 * batch] = pos;
+}
+
+// ---------------------------------------------------------------------------
+// The duration plan: the integer durations of every token under a caller's
+// controls, one 256-thread workgroup per row, no host sync.  A token x <
+// x_len is pinned (given[x] >= 0: exactly that many frames, 0 allowed) or
+// free.  A free token's w = ed_token_w(logw, rate) * tok_scale[x] (one more
+// fp16 rounding under half_round) and, without a target, d = ceil(w).
+//
+// With a target T (> 0) the free tokens are fitted so that the row sums to
+// exactly T, in integer arithmetic (rate is not applied: the target sets
+// the speed).  F = the free tokens, P = the sum of the pins, E = T - P - |F|
+// the frames to hand out beyond one per free token:
+//   q[x] = max(llrint(clamp(w, 2^-8, 2^15) * 256) - 128, 1)    (int64)
+//   Q[x] = inclusive prefix sum of q over F in token order, Qtot = its last
+//   B[x] = (Q[x] * E + Qtot / 2) / Qtot                        (int64 division)
+//   d[x] = 1 + B[x] - B[previous free token]                   (B = 0 before F)
+// so that sum_F d = |F| + B[last] = |F| + E: no sort, no dependence on the
+// summation order (integers), every free token >= 1.  A thread owns
+// consecutive tokens, so the B of the free token before its first one is the
+// B of its exclusive prefix of q.  q < 2^23, Qtot < 2^35, E <= DP_MAX_TARGET
+// = 2^24: the products stay below 2^60.
+//
+// status 1 (the row falls back to the no-target durations, rate applied):
+// E < 0, or no free token and T != P, or T > DP_MAX_TARGET.
+// Pins and ceil(w) are clamped to [0, ED_MAX_DUR = 2^18] (a NaN w: 0), the
+// clamp of the _int forms, so total and their y_len cannot disagree.
+// meta = [total (batch) | status (batch)]; total is the plain integer sum of
+// the row (no fp16 rounding, no max(., 1)); 4096 * 2^18 = 2^30 fits.
+// ---------------------------------------------------------------------------
+constexpr int DP_MAX_TARGET = 1 << 24;
+
+__device__ __forceinline__ long long dp_block_sum(long long v, long long* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  const long long r = red[0];
+  __syncthreads();  // red is reused
+  return r;
+}
+
+// exclusive prefix of v over the threads of the workgroup; `all` = the sum
+__device__ __forceinline__ long long dp_block_excl(long long v, long long* red, long long& all) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const long long a = tid >= o ? red[tid - o] : 0;
+    __syncthreads();
+    red[tid] += a;
+    __syncthreads();
+  }
+  const long long ex = tid > 0 ? red[tid - 1] : 0;
+  all = red[255];
+  __syncthreads();  // red is reused
+  return ex;
+}
+
+__device__ __forceinline__ long long dp_weight(float w) {
+  const float c = fminf(fmaxf(w, 0.00390625f), 32768.f);  // NaN -> 2^-8
+  const long long q = llrintf(c * 256.f) - 128;
+  return q > 1 ? q : 1;
+}
+
+__global__ __launch_bounds__(256) void duration_plan_kernel(
+    const float* __restrict__ logw, int64_t logw_bstride, const int32_t* __restrict__ x_len,
+    int t_x, float rate, const float* __restrict__ rates, int half_round,
+    const int32_t* __restrict__ given, const float* __restrict__ tok_scale,
+    const int32_t* __restrict__ target, int32_t* __restrict__ dur, int32_t* __restrict__ meta,
+    float* __restrict__ w_out, int batch) {
+  __shared__ long long red[256];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int nx = x_len ? min(max(x_len[b], 0), t_x) : t_x;
+  const float* lrow = logw + (int64_t)b * logw_bstride;
+  const int32_t* grow = given ? given + (int64_t)b * t_x : nullptr;
+  const float* srow = tok_scale ? tok_scale + (int64_t)b * t_x : nullptr;
+  int32_t* drow = dur + (int64_t)b * t_x;
+  float* wrow = w_out ? w_out + (int64_t)b * t_x : nullptr;
+  const int per = (t_x + 255) / 256;
+  const int x0 = tid * per;
+  const int x1 = min(x0 + per, nx);  // this thread's tokens: [x0, x1)
+
+  // 1) the pins: |F| and P, hence whether the target can be met
+  long long n_free = 0, pinned = 0;
+  for (int x = x0; x < x1; ++x) {
+    const int g = grow ? grow[x] : -1;
+    if (g >= 0) pinned += min(g, ED_MAX_DUR); else ++n_free;
+  }
+  n_free = dp_block_sum(n_free, red);
+  pinned = dp_block_sum(pinned, red);
+  const long long T = target ? target[b] : 0;
+  const long long E = T - pinned - n_free;
+  const bool has_target = T > 0;
+  const bool fit = has_target && T <= DP_MAX_TARGET && (n_free > 0 ? E >= 0 : T == pinned);
+  const float r = fit ? 1.0f : (rates ? rates[b] : rate);
+
+  // w of a free token (a fitted row: rate not applied)
+  auto token_w = [&](int x) {
+    float w = fit ? ed_token_w(lrow[x], 1.0f, half_round) : ed_token_w(lrow[x], r, half_round);
+    if (srow) {
+      w = w * srow[x];
+      if (half_round) w = (float)(_Float16)w;
+    }
+    return w;
+  };
+
+  // 2) fitted rows: this thread's share of Q
+  long long q_before = 0, q_all = 1;
+  if (fit) {  // (uniform over the workgroup)
+    long long q_local = 0;
+    for (int x = x0; x < x1; ++x)
+      if (!(grow && grow[x] >= 0)) q_local += dp_weight(token_w(x));
+    q_before = dp_block_excl(q_local, red, q_all);
+    if (q_all < 1) q_all = 1;  // (no free token: nothing is divided)
+  }
+
+  // 3) the durations
+  long long sum = 0;
+  long long Q = q_before;
+  long long b_prev = fit ? (Q * E + q_all / 2) / q_all : 0;
+  for (int x = x0; x < min(x0 + per, t_x); ++x) {
+    int d = 0;
+    float w = 0.f;
+    if (x < nx) {
+      const int g = grow ? grow[x] : -1;
+      if (g >= 0) {
+        d = min(g, ED_MAX_DUR);  // (what the _int forms would make of it)
+      } else {
+        w = token_w(x);
+        if (fit) {
+          Q += dp_weight(w);
+          const long long b_x = (Q * E + q_all / 2) / q_all;
+          d = (int)(1 + b_x - b_prev);
+          b_prev = b_x;
+        } else {
+          // ceil(w) within [0, ED_MAX_DUR]: an Inf or huge w (a large logw or
+          // scale) saturates instead of overflowing the conversion, a NaN or
+          // negative w lasts 0 frames
+          d = w > 0.f ? (w < (float)ED_MAX_DUR ? (int)ceilf(w) : ED_MAX_DUR) : 0;
+        }
+      }
+    }
+    drow[x] = d;
+    if (wrow) wrow[x] = w;
+    sum += d;
+  }
+  sum = dp_block_sum(sum, red);
+  if (tid == 0) {
+    meta[b] = (int32_t)(sum > 0x7FFFFFFFll ? 0x7FFFFFFFll : sum);
+    meta[batch + b] = has_target && !fit ? 1 : 0;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -568,17 +772,19 @@ extern "C" int vits_expand_prior(const float* attn, const float* m, const float*
   return vits_launch_status();
 }
 
-// rates == nullptr: every row runs at `rate`; else row b at rates[b] (device)
-static int ed_launch(const float* logw, int64_t logw_bstride, const int32_t* x_len, int t_x,
-                     float rate, const float* rates, int half_round, const float* m,
+// rates == nullptr: every row runs at `rate`; else row b at rates[b] (device);
+// kInt: src.dur int32 durations in place of logw / rate / half_round
+template <bool kInt>
+static int ed_launch(const EdSrc& src, const int32_t* x_len, int t_x, const float* m,
                      const float* s, int64_t ms_bstride, int32_t ms_cstride, const float* noise,
                      int noise_mode, const int32_t* noise_start, int64_t noise_len,
                      float noise_scale, float* z, int batch, int channels, int t_y, int32_t* lens,
                      const int32_t* stage_mult, int n_stage, void* stream) {
-  VITS_CHECK_ARG(logw && m && s && noise && z && lens && batch > 0 && channels > 0 && t_y > 0 &&
-                 t_x > 0);
+  VITS_CHECK_ARG((kInt ? (const void*)src.dur : (const void*)src.logw) && m && s && noise && z &&
+                 lens && batch > 0 && channels > 0 && t_y > 0 && t_x > 0);
   VITS_CHECK_ARG(n_stage >= 1 && n_stage <= ED_MAX_STAGES && (n_stage == 1 || stage_mult));
   VITS_CHECK_SHAPE(t_x <= ED_MAX_TX && ms_cstride >= t_x);
+  if (kInt) VITS_CHECK_SHAPE(src.bstride >= t_x);
   VITS_CHECK_ARG(noise_mode == 0 || ((noise_mode == 1 || noise_mode == 2) && noise_start));
   if (noise_mode == 2)  // int64 [batch] starts of vits_draw_starts
     VITS_CHECK_ARG((reinterpret_cast<uintptr_t>(noise_start) & 7) == 0 && noise_len > 0);
@@ -586,10 +792,9 @@ static int ed_launch(const float* logw, int64_t logw_bstride, const int32_t* x_l
   st.n = n_stage;
   for (int i = 0; i < ED_MAX_STAGES; ++i) st.mult[i] = i < n_stage ? (stage_mult ? stage_mult[i] : 1) : 0;
   dim3 grid((t_y + ED_T - 1) / ED_T, batch);
-  hipLaunchKernelGGL(expand_durations_kernel, grid, dim3(256), 0, as_stream(stream), logw,
-                     logw_bstride, x_len, t_x, rate, rates, half_round, m, s, ms_bstride,
-                     ms_cstride, noise, noise_mode, noise_start, noise_len, noise_scale, z,
-                     channels, t_y, batch, lens, st);
+  hipLaunchKernelGGL(expand_durations_kernel<kInt>, grid, dim3(256), 0, as_stream(stream), src,
+                     x_len, t_x, m, s, ms_bstride, ms_cstride, noise, noise_mode, noise_start,
+                     noise_len, noise_scale, z, channels, t_y, batch, lens, st);
   return vits_launch_status();
 }
 
@@ -601,9 +806,10 @@ extern "C" int vits_expand_durations(const float* logw, int64_t logw_bstride,
                                      float noise_scale, float* z,
                                      int batch, int channels, int t_y, int32_t* lens,
                                      const int32_t* stage_mult, int n_stage, void* stream) {
-  return ed_launch(logw, logw_bstride, x_len, t_x, rate, nullptr, half_round, m, s, ms_bstride,
-                   ms_cstride, noise, noise_mode, noise_start, noise_len, noise_scale, z, batch,
-                   channels, t_y, lens, stage_mult, n_stage, stream);
+  const EdSrc src{logw, nullptr, logw_bstride, rate, nullptr, half_round};
+  return ed_launch<false>(src, x_len, t_x, m, s, ms_bstride, ms_cstride, noise, noise_mode,
+                          noise_start, noise_len, noise_scale, z, batch, channels, t_y, lens,
+                          stage_mult, n_stage, stream);
 }
 
 extern "C" int vits_expand_durations_rows(const float* logw, int64_t logw_bstride,
@@ -616,22 +822,36 @@ extern "C" int vits_expand_durations_rows(const float* logw, int64_t logw_bstrid
                                           int t_y, int32_t* lens, const int32_t* stage_mult,
                                           int n_stage, void* stream) {
   VITS_CHECK_ARG(rates);
-  return ed_launch(logw, logw_bstride, x_len, t_x, 1.0f, rates, half_round, m, s, ms_bstride,
-                   ms_cstride, noise, noise_mode, noise_start, noise_len, noise_scale, z, batch,
-                   channels, t_y, lens, stage_mult, n_stage, stream);
+  const EdSrc src{logw, nullptr, logw_bstride, 1.0f, rates, half_round};
+  return ed_launch<false>(src, x_len, t_x, m, s, ms_bstride, ms_cstride, noise, noise_mode,
+                          noise_start, noise_len, noise_scale, z, batch, channels, t_y, lens,
+                          stage_mult, n_stage, stream);
 }
 
-static int ds_launch(const float* logw, int64_t logw_bstride, const int32_t* x_len, int t_x,
-                     float rate, const float* rates, int half_round, int channels,
+extern "C" int vits_expand_durations_int(const int32_t* dur, int64_t dur_bstride,
+                                         const int32_t* x_len, int t_x, const float* m,
+                                         const float* s, int64_t ms_bstride, int32_t ms_cstride,
+                                         const float* noise, int noise_mode,
+                                         const int32_t* noise_start, int64_t noise_len,
+                                         float noise_scale, float* z, int batch, int channels,
+                                         int t_y, int32_t* lens, const int32_t* stage_mult,
+                                         int n_stage, void* stream) {
+  const EdSrc src{nullptr, dur, dur_bstride, 1.0f, nullptr, 0};
+  return ed_launch<true>(src, x_len, t_x, m, s, ms_bstride, ms_cstride, noise, noise_mode,
+                         noise_start, noise_len, noise_scale, z, batch, channels, t_y, lens,
+                         stage_mult, n_stage, stream);
+}
+
+template <bool kInt>
+static int ds_launch(const EdSrc& src, const int32_t* x_len, int t_x, int channels,
                      int64_t noise_len, const uint32_t* pool, int pool_n, const int32_t* n_rows,
                      int batch, int64_t* starts, int32_t* meta, void* stream) {
-  VITS_CHECK_ARG(logw && pool && starts && meta && batch > 0 && channels > 0 && t_x > 0 &&
-                 pool_n > 0 && noise_len > 0);
+  VITS_CHECK_ARG((kInt ? (const void*)src.dur : (const void*)src.logw) && pool && starts && meta &&
+                 batch > 0 && channels > 0 && t_x > 0 && pool_n > 0 && noise_len > 0);
   VITS_CHECK_ARG((reinterpret_cast<uintptr_t>(starts) & 7) == 0);
-  VITS_CHECK_SHAPE(t_x <= ED_MAX_TX && batch <= 1024 && logw_bstride >= t_x);
-  hipLaunchKernelGGL(draw_starts_kernel, dim3(1), dim3(256), 0, as_stream(stream), logw,
-                     logw_bstride, x_len, t_x, rate, rates, half_round, channels, noise_len, pool,
-                     pool_n, n_rows, batch, starts, meta);
+  VITS_CHECK_SHAPE(t_x <= ED_MAX_TX && batch <= 1024 && src.bstride >= t_x);
+  hipLaunchKernelGGL(draw_starts_kernel<kInt>, dim3(1), dim3(256), 0, as_stream(stream), src,
+                     x_len, t_x, channels, noise_len, pool, pool_n, n_rows, batch, starts, meta);
   return vits_launch_status();
 }
 
@@ -640,8 +860,9 @@ extern "C" int vits_draw_starts(const float* logw, int64_t logw_bstride, const i
                                 int64_t noise_len, const uint32_t* pool, int pool_n,
                                 const int32_t* n_rows, int batch, int64_t* starts, int32_t* meta,
                                 void* stream) {
-  return ds_launch(logw, logw_bstride, x_len, t_x, rate, nullptr, half_round, channels, noise_len,
-                   pool, pool_n, n_rows, batch, starts, meta, stream);
+  const EdSrc src{logw, nullptr, logw_bstride, rate, nullptr, half_round};
+  return ds_launch<false>(src, x_len, t_x, channels, noise_len, pool, pool_n, n_rows, batch,
+                          starts, meta, stream);
 }
 
 extern "C" int vits_draw_starts_rows(const float* logw, int64_t logw_bstride,
@@ -650,8 +871,34 @@ extern "C" int vits_draw_starts_rows(const float* logw, int64_t logw_bstride,
                                      const uint32_t* pool, int pool_n, const int32_t* n_rows,
                                      int batch, int64_t* starts, int32_t* meta, void* stream) {
   VITS_CHECK_ARG(rates);
-  return ds_launch(logw, logw_bstride, x_len, t_x, 1.0f, rates, half_round, channels, noise_len,
-                   pool, pool_n, n_rows, batch, starts, meta, stream);
+  const EdSrc src{logw, nullptr, logw_bstride, 1.0f, rates, half_round};
+  return ds_launch<false>(src, x_len, t_x, channels, noise_len, pool, pool_n, n_rows, batch,
+                          starts, meta, stream);
+}
+
+extern "C" int vits_draw_starts_int(const int32_t* dur, int64_t dur_bstride, const int32_t* x_len,
+                                    int t_x, int channels, int64_t noise_len,
+                                    const uint32_t* pool, int pool_n, const int32_t* n_rows,
+                                    int batch, int64_t* starts, int32_t* meta, void* stream) {
+  const EdSrc src{nullptr, dur, dur_bstride, 1.0f, nullptr, 0};
+  return ds_launch<true>(src, x_len, t_x, channels, noise_len, pool, pool_n, n_rows, batch,
+                         starts, meta, stream);
+}
+
+// rates == nullptr: every row at `rate`.  given / tok_scale / dur / w_out are
+// contiguous [batch][t_x]; only logw has a row stride.
+extern "C" int vits_duration_plan(const float* logw, int64_t logw_bstride, const int32_t* x_len,
+                                  int t_x, float rate, const float* rates, int half_round,
+                                  const int32_t* given, const float* tok_scale,
+                                  const int32_t* target, int32_t* dur, int32_t* meta,
+                                  float* w_out, int batch, void* stream) {
+  VITS_CHECK_ARG(logw && dur && meta && batch > 0 && t_x > 0);
+  if (t_x > ED_MAX_TX) return VITS_E_UNSUP;
+  VITS_CHECK_SHAPE(logw_bstride >= t_x);
+  hipLaunchKernelGGL(duration_plan_kernel, dim3(batch), dim3(256), 0, as_stream(stream), logw,
+                     logw_bstride, x_len, t_x, rate, rates, half_round, given, tok_scale, target,
+                     dur, meta, w_out, batch);
+  return vits_launch_status();
 }
 
 extern "C" int vits_conv_post_tanh(const float* x, int64_t x_bstride, int32_t x_cstride,

@@ -18,6 +18,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
+from . import durations as dur_host
 from . import ops, utils
 from .commons import infer_path
 from .export import load_model
@@ -33,11 +34,15 @@ class PcmRequest:
     sampling_rate: Optional[int] = None
     volume: float = 1.0
     tail_silence: float = 0.0
+    # duration controls, one entry per item (None: no control for that item)
+    durations: Optional[Sequence] = None
+    token_scale: Optional[Sequence] = None
+    target_frames: Optional[Sequence] = None
 
 
 class EmoVITS(object):
     def __init__(self, checkpoint_path=None, device=None, *, loglv=0, hps=None, model=None,
-                 graph_cache=0, graph=True, max_graphs=16):
+                 graph_cache=0, graph=True, max_graphs=16, half=True):
         """graph: synthesise each utterance as ONE hipGraph replay
         (SynthesizerTrn.capture_infer_bucketed: the durations, the output
         length and the path computed on the device, no host sync before the
@@ -45,8 +50,12 @@ class EmoVITS(object):
         most ``max_graphs`` (the batched graphs of infer_batch /
         infer_pcm_batch and the rate-free ones of infer_pcm_requests
         included); graph=False: the reference's eager
-        sequence (infer_p1 -> host durations -> infer_p2)."""
+        sequence (infer_p1 -> host durations -> infer_p2).  half=False keeps
+        the model, its inputs and the noise buffer fp32 (the reference serves
+        fp16; the fp32 engine is the one whose bucketed and exact-length runs
+        agree bit for bit at every length)."""
         self.loglv = loglv
+        self.dtype = torch.float16 if half else torch.float32
         self.graph_cache = int(graph_cache)
         self._p1_graphs = {}
         self.graph = bool(graph)
@@ -82,8 +91,9 @@ class EmoVITS(object):
         if model is None:
             model = load_model(checkpoint_path, hps)
         model.remove_weight_norm()
-        self.model = model.half().eval().to(self.device)
-        self.noise = (torch.randn(1 * self.inter_channels * 4096) * self.noise_scale).half().to(self.device)
+        self.model = model.to(self.dtype).eval().to(self.device)
+        self.noise = (torch.randn(1 * self.inter_channels * 4096) * self.noise_scale).to(
+            self.dtype).to(self.device)
         self.inference = self.infer
         if self.device.type != "cuda":
             self.graph = False
@@ -166,7 +176,7 @@ class EmoVITS(object):
         spkid = self.spkid_mapping.get(spkid, spkid)
         assert spkid < self.num_speaker, f"spkid={spkid} must be less than {self.num_speaker}"
         if isinstance(emo, torch.Tensor):
-            emo = emo.half()
+            emo = emo.to(self.dtype)
         else:
             if emo is None:
                 emo = (spkid, -1)
@@ -174,36 +184,89 @@ class EmoVITS(object):
                 emo = tuple([self.spkid_mapping.get(emo[0], emo[0]) if emo[0] != 0 else spkid,
                              -1 if len(emo) == 1 else emo[1]])
             emo = self._get_spk_emo_embed(emo).unsqueeze(0)
-        return spkid, emo.to(self.device)
+        return spkid, emo.to(device=self.device, dtype=self.dtype)
 
     def _inputs(self, spkid, text, emo):
         x_length = text.shape[0]
         spkid, emo = self._resolve(spkid, emo)
         sid = torch.tensor([spkid], dtype=torch.long, device=self.device)
-        text_t = torch.from_numpy(np.ascontiguousarray(text)).half().to(self.device).unsqueeze(0)
+        text_t = torch.from_numpy(np.ascontiguousarray(text)).to(self.dtype).to(
+            self.device).unsqueeze(0)
         return x_length, text_t, emo, sid
 
-    def infer(self, spkid, text, emo, *, duration_rate=1.0):
-        x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
-        return self._infer_one(x_length, text_t, emo, sid, duration_rate), emo
+    @staticmethod
+    def _controls(x_length, durations, token_scale, target_frames, want=False):
+        """The duration controls of one utterance, checked on the host before
+        anything is uploaded (durations.check_controls raises ValueError):
+        None when there is none, else (given int32 [Tx] or None, scale fp32
+        [Tx] or None, target, known total or None).  ``want`` (the caller
+        asked for the durations back): the neutral controls instead of None,
+        so that the utterance takes the path that reports them."""
+        if durations is None and token_scale is None and target_frames is None and not want:
+            return None
+        return dur_host.check_controls(x_length, durations, token_scale, target_frames)
 
-    def _infer_one(self, x_length, text_t, emo, sid, duration_rate):
+    def infer(self, spkid, text, emo, *, duration_rate=1.0, durations=None, token_scale=None,
+              target_frames=None, return_durations=False):
+        """``durations`` (frames per token; < 0: left to the predictor),
+        ``token_scale`` (a factor >= 0 per token on the predicted durations)
+        and ``target_frames`` (the utterance lasts exactly that many frames;
+        ``duration_rate`` is then not applied) control the timing: the
+        durations come from ops.duration_plan inside the utterance graph
+        (graph mode) or from its host restatement (durations.plan_durations).
+        ``return_durations``: the frames per token as a third result.  The
+        plain graphs do not report durations, so in graph mode a call with
+        ``return_durations`` and no control replays the controlled graph with
+        neutral controls (one more cached graph per bucket pair; the same
+        samples, except that an fp16 model's plain call rounds a total above
+        2048 frames to fp16 and this one does not)."""
+        ctl = self._controls(text.shape[0], durations, token_scale, target_frames,
+                             return_durations)  # (refuses before anything is uploaded)
+        x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
+        got = [] if return_durations else None
+        wav = self._infer_one(x_length, text_t, emo, sid, duration_rate, ctl, got)
+        return (wav, emo, got[0]) if return_durations else (wav, emo)
+
+    def _infer_one(self, x_length, text_t, emo, sid, duration_rate, ctl=None, got=None):
         if self.graph and x_length <= 4096:
-            return self._infer_graph(text_t, emo, sid, duration_rate)
-        wav = self._infer_eager(x_length, text_t, emo, sid, duration_rate)
+            return self._infer_graph(text_t, emo, sid, duration_rate, ctl=ctl, got=got)
+        wav = self._infer_eager(x_length, text_t, emo, sid, duration_rate, ctl, got)
         return wav.float().view(-1).cpu().numpy()
 
-    def _infer_eager(self, x_length, text_t, emo, sid, duration_rate):
+    def _host_durations(self, logw, duration_rate, ctl):
+        """w_ceil [1, 1, Tx] of the eager path: ceil(exp(logw) * rate) in the
+        model's dtype (the reference sums it in that dtype), or under controls
+        the duration plan's rule on the host, fp32 integers, in the arithmetic
+        of the device plan (the model's dtype for exp, the rate and the scale;
+        the target drops the rate)."""
+        if ctl is None:
+            return torch.ceil(torch.exp(logw) * duration_rate)
+        given, scale, target, _ = ctl
+        if isinstance(given, torch.Tensor):
+            given = given.cpu().numpy()
+        w = torch.exp(logw)
+        if not target:
+            w = w * duration_rate
+        if scale is not None:
+            w = (w.float() * torch.from_numpy(scale).to(w.device).view(1, 1, -1)).to(logw.dtype)
+        d, _ = dur_host.plan_durations(w.float().view(-1).cpu().numpy(), given, target)
+        return torch.from_numpy(d.astype(np.float32)).to(logw.device).view(1, 1, -1)
+
+    def _infer_eager(self, x_length, text_t, emo, sid, duration_rate, ctl=None, got=None):
         """The reference's sequence: infer_p1 -> host durations -> infer_p2;
         the waveform stays on the device."""
         m_p, s_p, logw, g = self._infer_p1(text_t, emo, sid)
-        w = torch.exp(logw) * duration_rate
-        w_ceil = torch.ceil(w)
+        w_ceil = self._host_durations(logw, duration_rate, ctl)
+        if got is not None:
+            got.append(w_ceil.view(-1).cpu().numpy().astype(np.int32))
         y_length = int(torch.clamp_min(torch.sum(w_ceil), 1).item())
+        if ctl is not None and y_length > dur_host.MAX_FRAMES:
+            raise ValueError(f"utterance of {y_length} frames is over the limit of "
+                             f"{dur_host.MAX_FRAMES}")
         nl = self.inter_channels * y_length
         start = np.random.randint(max(1, self.noise.size(0) - nl))
         noise = self.noise[start:start + nl].view(1, self.inter_channels, y_length)
-        attn = infer_path(w_ceil.float(), x_length, y_length).half()
+        attn = infer_path(w_ceil.float(), x_length, y_length).to(self.dtype)
         return self.model.infer_p2(attn, m_p, s_p, g, noise)
 
     def _post_passes(self, pitch, sampling_rate):
@@ -248,7 +311,8 @@ class EmoVITS(object):
         return ops.pcm16(x, volume, lengths=lengths, length_scale=length_scale, out=pcm)
 
     def infer_pcm(self, spkid, text, emo, *, duration_rate=1.0, pitch=1.0, sampling_rate=None,
-                  volume=1.0, tail_silence=0.0):
+                  volume=1.0, tail_silence=0.0, durations=None, token_scale=None,
+                  target_frames=None, return_durations=False):
         """infer plus the output stage of VITSWrap.speaking (vits_wrap.py:
         186-197) on the device: pitch / sampling-rate resampling
         (ops.resample_poly), volume, clip and int16 conversion, tail silence.
@@ -257,20 +321,47 @@ class EmoVITS(object):
         whole bucket, with the length read from the graph's y_len on the
         device; the one host sync stays the y_len read.  Draws from numpy's
         generator exactly as infer does.  On a CPU device: infer and the host
-        chain.  Returns (pcm int16 [n], emo, n_model_samples)."""
+        chain.  ``durations`` / ``token_scale`` / ``target_frames`` /
+        ``return_durations`` as in infer (the durations are then a fourth
+        result).  Returns (pcm int16 [n], emo, n_model_samples)."""
         sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
+        ctl = self._controls(text.shape[0], durations, token_scale, target_frames,
+                             return_durations)  # (refuses before anything is uploaded)
         x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
+        got = [] if return_durations else None
         pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, duration_rate, pitch,
-                                     sampling_rate, volume, tail_silence)
-        return pcm, emo, n
+                                     sampling_rate, volume, tail_silence, ctl, got)
+        return (pcm, emo, n, got[0]) if return_durations else (pcm, emo, n)
+
+    def infer_pcm_like(self, wav, spkid_src, spkid, text, emo, *, sampling_rate_in=None,
+                       pitch=1.0, sampling_rate=None, volume=1.0, tail_silence=0.0,
+                       return_durations=False):
+        """``text`` spoken by ``spkid`` with the timing of the recording
+        ``wav`` of speaker ``spkid_src`` saying it: an alignment graph replay
+        (align's) whose durations are copied device to device into the
+        controlled synthesis graph's ``given`` buffer, then that replay and
+        infer_pcm's output stage.  The durations do not visit the host on
+        the way; what comes back is what ``align`` followed by
+        ``infer_pcm(durations=...)`` returns, sample for sample, with numpy's
+        generator left in the same state.  The frame bucket comes from the
+        recording's frame count, which the host knows.  Needs a ROCm GPU."""
+        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
+        text = np.ascontiguousarray(text)
+        (dur, frames), = self._align_rows([wav], [spkid_src], [text], [emo], sampling_rate_in,
+                                          0.0, device=True)
+        x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
+        got = [] if return_durations else None
+        pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, 1.0, pitch, sampling_rate,
+                                     volume, tail_silence, (dur, None, 0, int(frames)), got)
+        return (pcm, emo, n, got[0]) if return_durations else (pcm, emo, n)
 
     def _infer_pcm_one(self, x_length, text_t, emo, sid, duration_rate, pitch, sampling_rate,
-                       volume, tail_silence):
+                       volume, tail_silence, ctl=None, got=None):
         tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
         if self.device.type != "cuda":
             from . import vits_wrap
 
-            wav = self._infer_one(x_length, text_t, emo, sid, duration_rate)
+            wav = self._infer_one(x_length, text_t, emo, sid, duration_rate, ctl, got)
             pcm = vits_wrap.host_pcm(wav, self.sampling_rate, pitch, sampling_rate, volume,
                                      tail_silence)
             return pcm, len(wav)
@@ -279,10 +370,11 @@ class EmoVITS(object):
             pcm, n = self._infer_graph(
                 text_t, emo, sid, duration_rate,
                 post=lambda wav, y_len: self._post(wav, passes, volume, tail, lengths=y_len,
-                                                   length_scale=self.hop_size))
+                                                   length_scale=self.hop_size),
+                ctl=ctl, got=got)
             n *= self.hop_size
         else:
-            wav = self._infer_eager(x_length, text_t, emo, sid, duration_rate)
+            wav = self._infer_eager(x_length, text_t, emo, sid, duration_rate, ctl, got)
             n = wav.shape[-1]
             pcm = self._post(wav.reshape(1, -1), passes, volume, tail, lengths=n)
         n_out = n
@@ -323,16 +415,44 @@ class EmoVITS(object):
 
     def _one_tensors(self, spkid, text):
         sid = torch.tensor([spkid], dtype=torch.long, device=self.device)
-        return text.shape[0], torch.from_numpy(text).half().to(self.device).unsqueeze(0), sid
+        return text.shape[0], torch.from_numpy(text).to(self.dtype).to(self.device).unsqueeze(0), sid
 
-    def infer_batch(self, items, *, duration_rate=1.0):
+    def _item_controls(self, items, durations, token_scale, target_frames, want=False):
+        """_controls of every item of a batch call (per-item lists or None),
+        checked before any item is looked up or uploaded."""
+        n = len(items)
+        cols = []
+        for name, v in (("durations", durations), ("token_scale", token_scale),
+                        ("target_frames", target_frames)):
+            v = [None] * n if v is None else list(v)
+            if len(v) != n:
+                raise ValueError(f"{name}: need one entry per item ({n}), got {len(v)}")
+            cols.append(v)
+        return [self._controls(np.shape(items[i][1])[0], cols[0][i], cols[1][i], cols[2][i], want)
+                for i in range(n)]
+
+    @staticmethod
+    def _header(B, extra=0):
+        """int16 elements in front of a packed group's samples: the int32
+        words [offsets (B + 1) | y_len, status, used_total (2 B + 1) | extra
+        (the durations of a controlled group)], rounded to 16 bytes."""
+        return -(-2 * (3 * B + 2 + extra) // 8) * 8
+
+    def infer_batch(self, items, *, duration_rate=1.0, durations=None, token_scale=None,
+                    target_frames=None, return_durations=False):
         """infer for items = [(spkid, text [N, c], emo), ...]: [(wav float32
         [n], emo), ...], bit for bit what a loop over infer returns for emo
         tensors (see _resolve_items for the order of numpy draws otherwise),
         with numpy's generator left where the loop leaves it.  Groups of up
         to MAX_BATCH items run as ONE replay of a batched utterance graph
         (batch buckets 2, 4, 8, 16); a single item, a CPU device or
-        graph=False run infer's path per item."""
+        graph=False run infer's path per item.  ``durations`` /
+        ``token_scale`` / ``target_frames``: per-item lists (None entries:
+        no control) as in infer; a control on any row of a group routes the
+        group to a graph cached under ("ctl", batch bucket, text bucket,
+        frame bucket).  ``return_durations``: (wav, emo, durations) tuples."""
+        items = list(items)
+        ctls = self._item_controls(items, durations, token_scale, target_frames, return_durations)
         texts, spkids, emos = self._resolve_items(items)
         if not texts:
             return []
@@ -341,18 +461,23 @@ class EmoVITS(object):
             if hi - lo == 1 or not self._batchable(texts[lo:hi]):
                 for i in range(lo, hi):
                     x_length, text_t, sid = self._one_tensors(spkids[i], texts[i])
-                    out.append((self._infer_one(x_length, text_t, emos[i], sid, duration_rate),
-                                emos[i]))
+                    got = [] if return_durations else None
+                    wav = self._infer_one(x_length, text_t, emos[i], sid, duration_rate, ctls[i],
+                                          got)
+                    out.append((wav, emos[i]) + ((got[0],) if return_durations else ()))
                 continue
+            durs = []
             wav, y = self._infer_graph_batch(texts[lo:hi], emos[lo:hi], spkids[lo:hi],
-                                             duration_rate)
+                                             duration_rate, ctls=ctls[lo:hi], got=durs)
             hop = self.hop_size
             host = wav[:hi - lo, 0, :max(y) * hop].cpu()  # one copy for the group
-            out += [(host[i, :n * hop].float().numpy(), emos[lo + i]) for i, n in enumerate(y)]
+            out += [(host[i, :n * hop].float().numpy(), emos[lo + i])
+                    + ((durs[i],) if return_durations else ()) for i, n in enumerate(y)]
         return out
 
     def infer_pcm_batch(self, items, *, duration_rate=1.0, pitch=1.0, sampling_rate=None,
-                        volume=1.0, tail_silence=0.0):
+                        volume=1.0, tail_silence=0.0, durations=None, token_scale=None,
+                        target_frames=None, return_durations=False):
         """infer_pcm for items = [(spkid, text, emo), ...] that share one
         rate, pitch, sampling rate, volume and tail: (pcm int16 [total],
         offsets int64 [len + 1], emos, n_model list).  Item i's PCM, its tail
@@ -361,46 +486,62 @@ class EmoVITS(object):
         over infer_pcm leaves it.  A group of up to MAX_BATCH items is one
         graph replay, the post passes over all its rows, the ragged pack
         (ops.pack_pcm) and ONE device-to-host copy with the one host sync:
-        offsets, lengths and draw status arrive in front of the samples."""
+        offsets, lengths and draw status arrive in front of the samples.
+        ``durations`` / ``token_scale`` / ``target_frames``: per-item lists
+        as in infer_batch; a controlled group's final durations ride in the
+        same copy, behind the header words, and come back as a fifth result
+        (a list of int32 arrays) with ``return_durations``."""
         sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
         tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
+        items = list(items)
+        ctls = self._item_controls(items, durations, token_scale, target_frames, return_durations)
         texts, spkids, emos = self._resolve_items(items)
-        chunks, offsets, n_model = [], [0], []
+        chunks, offsets, n_model, durs = [], [0], [], []
         for lo, hi in self._groups(len(texts)):
             if hi - lo == 1 or not self._batchable(texts[lo:hi]):
                 for i in range(lo, hi):
                     x_length, text_t, sid = self._one_tensors(spkids[i], texts[i])
+                    got = [] if return_durations else None
                     pcm, n = self._infer_pcm_one(x_length, text_t, emos[i], sid, duration_rate,
-                                                 pitch, sampling_rate, volume, tail_silence)
+                                                 pitch, sampling_rate, volume, tail_silence,
+                                                 ctls[i], got)
                     chunks.append(pcm)
                     offsets.append(offsets[-1] + len(pcm))
                     n_model.append(n)
+                    durs += got or []
                 continue
             passes = self._post_passes(pitch, sampling_rate)
             (pcm, offs), y = self._infer_graph_batch(
                 texts[lo:hi], emos[lo:hi], spkids[lo:hi], duration_rate,
-                post=lambda wav, y_len, n_rows, words: self._post_pack(
-                    wav, y_len, n_rows, words, passes, volume, tail))
+                post=lambda wav, y_len, n_rows, words, extra=None: self._post_pack(
+                    wav, y_len, n_rows, words, passes, volume, tail, extra),
+                ctls=ctls[lo:hi], got=durs)
             chunks.append(pcm)
             offsets += [offsets[-1] + int(o) for o in offs[1:]]
             n_model += [n * self.hop_size for n in y]
         pcm = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int16)
-        return pcm, np.asarray(offsets, dtype=np.int64), emos, n_model
+        out = (pcm, np.asarray(offsets, dtype=np.int64), emos, n_model)
+        return out + (durs,) if return_durations else out
 
-    def _post_pack(self, wav, y_len, n_rows, words, passes, volume, tail):
+    def _post_pack(self, wav, y_len, n_rows, words, passes, volume, tail, extra=None):
         """The post passes over every row of the bucket, then the ragged
         pack: one int16 buffer, in front of the samples the int32 words
-        [offsets (B + 1) | words (y_len, status, used_total: 2 B + 1)]."""
+        [offsets (B + 1) | words (y_len, status, used_total: 2 B + 1) |
+        extra (int32, a controlled group's durations)]."""
         B = wav.shape[0]
         rows = self._post(wav, passes, volume, tail, lengths=y_len, length_scale=self.hop_size)
-        header = -(-2 * (3 * B + 2) // 8) * 8
+        n_extra = 0 if extra is None else extra.numel()
+        header = self._header(B, n_extra)
         out, _, _ = ops.pack_pcm(rows, y_len, self.hop_size, passes, tail, n_rows=n_rows,
                                  header=header)
         torch.cat(words, out=out[2 * (B + 1):2 * (3 * B + 2)].view(torch.int32))
+        if n_extra:
+            out[2 * (3 * B + 2):2 * (3 * B + 2 + n_extra)].view(torch.int32).copy_(
+                extra.reshape(-1))
         return out
 
     # -- mixed requests: rows with their own speed, pitch, rate, volume, tail ------
-    def infer_pcm_requests(self, requests):
+    def infer_pcm_requests(self, requests, *, return_durations=False):
         """infer_pcm_batch for several requests at once, each a PcmRequest
         with its own controls: one (pcm, offsets, emos, n_model) per request,
         what ``infer_pcm_batch(r.items, **controls)`` returns for it when the
@@ -418,25 +559,35 @@ class EmoVITS(object):
         (ops.resample_rows: a row with fewer passes copies in the slot it
         does not use), the per-row pack (ops.pack_pcm_rows) and ONE
         device-to-host copy.  A group of one row, a CPU device or graph=False
-        run infer_pcm's path per row."""
+        run infer_pcm's path per row.  A request's ``durations`` /
+        ``token_scale`` / ``target_frames`` (per-item lists) control its
+        rows as in infer_pcm_batch; controlled and plain rows share a group.
+        ``return_durations``: a fifth entry per request, its rows' durations."""
         requests = list(requests)
+        row_ctl = []
+        for r in requests:  # every check before any lookup or upload
+            row_ctl += self._item_controls(list(r.items), r.durations, r.token_scale,
+                                           r.target_frames, return_durations)
         rows, spans = [], []  # per row: (text, spkid, emo, request); per request: (lo, hi, emos)
         for r in requests:
             texts, spkids, emos = self._resolve_items(r.items)
             spans.append((len(rows), len(rows) + len(texts), emos))
             rows += [(t, s, e, r) for t, s, e in zip(texts, spkids, emos)]
-        pcms, n_model = [], []
+        pcms, n_model, durs = [], [], []
         for lo, hi in self._groups(len(rows)):
             group = rows[lo:hi]
             ctl = [(self.sampling_rate if r.sampling_rate is None else int(r.sampling_rate), r)
                    for _, _, _, r in group]
             if hi - lo == 1 or not self._batchable([t for t, _, _, _ in group]):
-                for (text, spkid, emo, r), (sr, _) in zip(group, ctl):
+                for j, ((text, spkid, emo, r), (sr, _)) in enumerate(zip(group, ctl)):
                     x_length, text_t, sid = self._one_tensors(spkid, text)
+                    got = [] if return_durations else None
                     pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, r.duration_rate,
-                                                 r.pitch, sr, r.volume, r.tail_silence)
+                                                 r.pitch, sr, r.volume, r.tail_silence,
+                                                 row_ctl[lo + j], got)
                     pcms.append(pcm)
                     n_model.append(n)
+                    durs += got or []
                 continue
             passes = [self._post_passes(r.pitch, sr) for sr, r in ctl]
             volumes = [r.volume for _, r in ctl]
@@ -444,18 +595,20 @@ class EmoVITS(object):
             (pcm, offs), y = self._infer_graph_batch(
                 [t for t, _, _, _ in group], [e for _, _, e, _ in group],
                 [s for _, s, _, _ in group], None, rates=[r.duration_rate for _, r in ctl],
-                post=lambda wav, y_len, n_rows, words: self._post_pack_rows(
-                    wav, y_len, n_rows, words, passes, volumes, tails))
+                post=lambda wav, y_len, n_rows, words, extra=None: self._post_pack_rows(
+                    wav, y_len, n_rows, words, passes, volumes, tails, extra),
+                ctls=row_ctl[lo:hi], got=durs)
             pcms += [pcm[int(offs[i]):int(offs[i + 1])] for i in range(hi - lo)]
             n_model += [n * self.hop_size for n in y]
         out = []
         for lo, hi, emos in spans:
             offsets = np.cumsum([0] + [len(p) for p in pcms[lo:hi]]).astype(np.int64)
             pcm = np.concatenate(pcms[lo:hi]) if hi > lo else np.zeros(0, dtype=np.int16)
-            out.append((pcm, offsets, emos, n_model[lo:hi]))
+            out.append((pcm, offsets, emos, n_model[lo:hi])
+                       + ((durs[lo:hi],) if return_durations else ()))
         return out
 
-    def _post_pack_rows(self, wav, y_len, n_rows, words, passes, volumes, tails):
+    def _post_pack_rows(self, wav, y_len, n_rows, words, passes, volumes, tails, extra=None):
         """_post_pack with per-row controls: ``passes`` / ``volumes`` /
         ``tails`` of the group's rows (the padding rows of the bucket copy at
         volume 1 with no tail).  max(1, most passes of a row) launches of
@@ -481,10 +634,14 @@ class EmoVITS(object):
         pcm = torch.empty(B, max(1, max(caps) + max(tails)), device=wav.device, dtype=torch.int16)
         ops.resample_rows(x, ratios, lengths=lengths, length_scale=scale, volumes=volumes,
                           pcm=True, out=pcm)
-        header = -(-2 * (3 * B + 2) // 8) * 8
+        n_extra = 0 if extra is None else extra.numel()
+        header = self._header(B, n_extra)
         out, _, _ = ops.pack_pcm_rows(pcm, y_len, self.hop_size, passes, tails, n_rows=n_rows,
                                       header=header)
         torch.cat(words, out=out[2 * (B + 1):2 * (3 * B + 2)].view(torch.int32))
+        if n_extra:
+            out[2 * (3 * B + 2):2 * (3 * B + 2 + n_extra)].view(torch.int32).copy_(
+                extra.reshape(-1))
         return out
 
     def _to_host(self, t):
@@ -499,7 +656,8 @@ class EmoVITS(object):
         torch.cuda.current_stream(self.device).synchronize()
         return buf[:n].numpy().copy()
 
-    def _infer_graph_batch(self, texts, emos, spkids, duration_rate, post=None, rates=None):
+    def _infer_graph_batch(self, texts, emos, spkids, duration_rate, post=None, rates=None,
+                           ctls=None, got=None):
         """2..16 utterances as one replay of a batched utterance graph, cached
         with the B = 1 graphs per (batch bucket, text bucket, frame bucket,
         rate); with ``rates`` (one speed per row; ``duration_rate`` unused)
@@ -513,34 +671,62 @@ class EmoVITS(object):
         used_total))`` -> the int16 buffer of _post_pack: ((pcm, offsets),
         y_len list) on the host after its single copy.  A row longer than the
         frame bucket re-runs the group at a larger bucket (same draws), an
-        exhausted pool re-runs it with a pool twice as long."""
+        exhausted pool re-runs it with a pool twice as long.
+
+        ``ctls`` (per row: the result of _controls, or None) with a control
+        on any row: the group replays a controlled, rate-free graph cached
+        under ("ctl", batch bucket, text bucket, frame bucket); rows without
+        a control get the neutral one.  The frame bucket is at least what the
+        rows whose total the host knows need.  The final durations [B, text
+        bucket] ride behind the header words of the packed buffer (``post`` is
+        then called with them as ``extra``), or with the words when there is
+        no post, and row i's int32 [t_x_i] is appended to ``got``."""
         n = len(texts)
+        controlled = ctls is not None and any(c is not None for c in ctls)
+        if controlled and rates is None:
+            rates = [duration_rate] * n
         bb = self._batch_bucket(n)
         lengths = [t.shape[0] for t in texts]
         xb = -(-max(lengths) // self.TX_BUCKET) * self.TX_BUCKET
         x = np.zeros((n, max(lengths), texts[0].shape[1]), dtype=np.float32)
         for i, t in enumerate(texts):
             x[i, :lengths[i]] = t
-        x = torch.from_numpy(x).half().to(self.device)
+        x = torch.from_numpy(x).to(self.dtype).to(self.device)
         emo = torch.cat(emos)
         sid = torch.tensor(spkids, dtype=torch.long)
         pool_mult = 1
         memo = (bb, xb, duration_rate) if rates is None else ("rows", bb, xb)
+        control, known = None, 0
+        if controlled:
+            memo = ("ctl", bb, xb)
+            rows = [c if c is not None else (None, None, 0, None) for c in ctls]
+            control = dict(given=[c[0] for c in rows], tok_scale=[c[1] for c in rows],
+                           target=[c[2] for c in rows])
+            known = max([c[3] or 0 for c in rows])
         while True:
             tyb = self._ty_bucket.get(memo, 256)
+            if known > tyb:
+                tyb = 1 << (known - 1).bit_length()
             key = (bb, xb, tyb, float(duration_rate)) if rates is None else ("rows", bb, xb, tyb)
+            if controlled:
+                key = ("ctl", bb, xb, tyb)
             run = self._graphs.pop(key, None)
             if run is None:
                 while len(self._graphs) >= self.max_graphs:
                     self._graphs.pop(next(iter(self._graphs)))
                 run = self.model.capture_infer_bucketed(
                     xb, tyb, noise_len=self.noise.numel(), padded_text=True, batch=bb,
-                    length_scale=duration_rate if rates is None else torch.ones(bb))
+                    length_scale=duration_rate if rates is None else torch.ones(bb),
+                    control=controlled)
                 run.static["noise"].copy_(self.noise.float())
             self._graphs[key] = run  # most recently used last
             pool, state = ops.numpy_draw_pool(run.pool_len * pool_mult)
+            dur = None
             if pool_mult == 1:
-                if rates is None:
+                if controlled:
+                    wav, y_len, status, used, dur, _ = run(x, emo, sid, lengths, pool, n,
+                                                           rates=rates, control=control)
+                elif rates is None:
                     wav, y_len, status, used = run(x, emo, sid, lengths, pool, n)
                 else:
                     wav, y_len, status, used = run(x, emo, sid, lengths, pool, n, rates=rates)
@@ -548,19 +734,25 @@ class EmoVITS(object):
                 # the graph's pool is static: the (p < 2^-32 per row) longer
                 # pool runs the same kernels eagerly on the graph's inputs
                 st = run.static
-                wav, y_len, status, used = self.model.infer_bucketed(
+                res = self.model.infer_bucketed(
                     st["x"], st["emo"], st["sid"], st["noise"], tyb, x_lengths=st["xl"],
                     length_scale=duration_rate if rates is None else st["rates"],
-                    noise_start=torch.from_numpy(pool).to(self.device), n_rows=st["n_rows"])
+                    noise_start=torch.from_numpy(pool).to(self.device), n_rows=st["n_rows"],
+                    control={k: st[k] for k in ("given", "tok_scale", "target")}
+                    if controlled else None)
+                wav, y_len, status, used = res[:4]
+                dur = res[4] if controlled else None
             words = (y_len, status, used)
+            n_extra = bb * xb if controlled else 0
             if post is None:
-                host = torch.cat(words).tolist()  # (synchronises)
+                host = torch.cat(words + ((dur.reshape(-1),) if controlled else ())).tolist()
             else:
-                packed = post(wav[:, 0], y_len, run.static["n_rows"], words)
-                header = -(-2 * (3 * bb + 2) // 8) * 8
+                packed = (post(wav[:, 0], y_len, run.static["n_rows"], words, dur) if controlled
+                          else post(wav[:, 0], y_len, run.static["n_rows"], words))
+                header = self._header(bb, n_extra)
                 row_cap = (packed.numel() - header) // bb  # (the padding rows hold nothing)
                 buf = self._to_host(packed[:header + n * row_cap])
-                host = buf[2 * (bb + 1):2 * (3 * bb + 2)].view(np.int32).tolist()
+                host = buf[2 * (bb + 1):2 * (3 * bb + 2 + n_extra)].view(np.int32).tolist()
             y, st_rows, used = host[:n], host[bb:bb + n], host[2 * bb]
             if max(y) > tyb:
                 np.random.set_state(state)  # re-run at a larger bucket: same draws
@@ -578,6 +770,9 @@ class EmoVITS(object):
                 raise ValueError(f"utterance of {y[st_rows.index(-1)]} frames does not fit the "
                                  f"{self.noise.numel()}-sample noise buffer")
             ops.numpy_draw_commit(state, used)
+            if controlled and got is not None:
+                d = np.asarray(host[2 * bb + 1:2 * bb + 1 + n_extra], np.int32).reshape(bb, xb)
+                got += [d[i, :lengths[i]].copy() for i in range(n)]
             if post is None:
                 return wav, y
             offs = buf[:2 * (bb + 1)].view(np.int32)[:n + 1]
@@ -784,13 +979,14 @@ class EmoVITS(object):
     # the widest text the alignment kernel takes (vits_maximum_path_durations)
     ALIGN_MAX_TOKENS = 2048
 
-    def _align_rows(self, wavs, spkids, texts, emos, sampling_rate_in, noise_scale):
+    def _align_rows(self, wavs, spkids, texts, emos, sampling_rate_in, noise_scale, device=False):
         """1 .. MAX_BATCH (recording, text) pairs through one alignment graph,
         cached in self._graphs under ("align", batch bucket, text bucket,
         frame bucket) (graph=False: the same align_bucketed call, eagerly).
         Returns [(durations int32 [Tx], scores fp32 [Tx], frames)] on the host
         after ONE device-to-host copy.  The host knows every length: a
-        recording with fewer frames than tokens is refused here."""
+        recording with fewer frames than tokens is refused here.  ``device``:
+        [(durations int32 [Tx] on the device, frames)] with no copy at all."""
         if self.device.type != "cuda":
             raise ops._lib.VitsAmdError("EmoVITS.align: the vits_amd inference path runs on a "
                                         f"ROCm GPU only (got {self.device})")
@@ -821,7 +1017,7 @@ class EmoVITS(object):
         x = np.zeros((n, max(tokens), np.shape(texts[0])[1]), dtype=np.float32)
         for i, t in enumerate(texts):
             x[i, :tokens[i]] = t
-        x = torch.from_numpy(x).half().to(self.device)
+        x = torch.from_numpy(x).to(self.dtype).to(self.device)
         noise = None
         if noise_scale > 0:
             if self._vc_gen is None:
@@ -854,6 +1050,8 @@ class EmoVITS(object):
                 ws, torch.tensor(lens + pad, dtype=torch.int32).to(dev), xs,
                 torch.tensor(tokens + pad, dtype=torch.int32).to(dev), es,
                 torch.tensor(sids + pad, dtype=torch.long).to(dev), nz, xb, tyb, stft=stft)
+        if device:  # (infer_pcm_like: the durations stay on the device, nothing is copied)
+            return [(dur[i, :tokens[i]], frames[i]) for i in range(n)]
         host = self._to_host(torch.cat([dur[:n], scores[:n].view(torch.int32)], 1)).reshape(n, -1)
         return [(host[i, :tokens[i]].copy(), host[i, xb:xb + tokens[i]].view(np.float32).copy(),
                  frames[i]) for i in range(n)]
@@ -893,35 +1091,59 @@ class EmoVITS(object):
     # frame buckets are powers of two from 256 up to the noise buffer's 4096
     TX_BUCKET = 32
 
-    def _infer_graph(self, text_t, emo, sid, duration_rate, post=None):
+    def _infer_graph(self, text_t, emo, sid, duration_rate, post=None, ctl=None, got=None):
         """One replay of the whole-utterance graph; the one host sync is the
         waveform copy (y_len read with it).  A bucket that turns out too
         small (y_len > frames) is re-run once at a large enough bucket,
         which this text bucket keeps from then on.  ``post(wav [1, frames *
         hop], y_len int32 [1])`` is launched behind every replay, before the
         sync; its result is then returned with the frame count, in place of
-        the waveform."""
+        the waveform.
+
+        ``ctl`` (the result of _controls): the utterance runs through a
+        controlled, rate-free graph cached under ("ctl", 1, text bucket, frame
+        bucket) in the same most-recently-used cache; the speed and the
+        controls are replay inputs, so one graph serves every control.  When
+        the host knows the total (a target, or every token pinned) the frame
+        bucket is chosen from it; else the bucket is remembered per text
+        bucket and grown by the re-run below.  ``got`` (a list): the final
+        durations (int32 [t_x]) are appended to it."""
         t_x = text_t.shape[1]
         xb = -(-t_x // self.TX_BUCKET) * self.TX_BUCKET
+        memo = (xb, duration_rate) if ctl is None else ("ctl", xb)
         while True:
-            tyb = self._ty_bucket.get((xb, duration_rate), 256)
-            key = (xb, tyb, float(duration_rate))
+            tyb = self._ty_bucket.get(memo, 256)
+            if ctl is not None and ctl[3] is not None:
+                tyb = max(256, 1 << (max(ctl[3], 1) - 1).bit_length())
+            key = (xb, tyb, float(duration_rate)) if ctl is None else ("ctl", 1, xb, tyb)
             run = self._graphs.pop(key, None)
             if run is None:
                 while len(self._graphs) >= self.max_graphs:
                     self._graphs.pop(next(iter(self._graphs)))
                 run = self.model.capture_infer_bucketed(
                     xb, tyb, noise_len=self.noise.numel(), padded_text=True,
-                    length_scale=duration_rate)
+                    length_scale=duration_rate, control=ctl is not None)
                 run.static["noise"].copy_(self.noise.float())
             self._graphs[key] = run  # most recently used last
             # infer.py:173's np.random.randint(len - nl), drawn on the device
             # from raw words of numpy's own generator: the same start as the
             # reference, and the generator ends where the reference's does
             pool, state = ops.numpy_draw_pool()
-            wav, y_len = run(text_t, emo, sid, noise_start=pool, x_length=t_x)
+            if ctl is None:
+                wav, y_len = run(text_t, emo, sid, noise_start=pool, x_length=t_x)
+            else:
+                wav, y_len, dur, _ = run(
+                    text_t, emo, sid, noise_start=pool, x_length=t_x, rate=duration_rate,
+                    control=dict(given=ctl[0], tok_scale=ctl[1], target=ctl[2]))
             posted = None if post is None else post(wav[0], y_len[0])
-            n, used = (int(v) for v in y_len[:, 0].tolist())  # (synchronises)
+            if ctl is None:
+                n, used = (int(v) for v in y_len[:, 0].tolist())  # (synchronises)
+            else:  # the durations ride in the y_len read: still one small copy
+                host = torch.cat([y_len[:, 0], dur[0, :t_x]]).tolist()
+                n, used = host[:2]
+                if got is not None and n <= tyb:
+                    del got[:]
+                    got.append(np.asarray(host[2:], np.int32))
             if n <= tyb and used == -2:
                 # every word of the pool was rejected (p < 2^-32): numpy's
                 # randint would go on drawing - advance past the pool and
@@ -940,7 +1162,7 @@ class EmoVITS(object):
             np.random.set_state(state)  # re-run at a larger bucket: same draw
             if tyb >= 4096:
                 raise RuntimeError(f"utterance of {n} frames exceeds the 4096-frame noise buffer")
-            self._ty_bucket[(xb, duration_rate)] = min(4096, 1 << (n - 1).bit_length())
+            self._ty_bucket[memo] = min(4096, 1 << (n - 1).bit_length())
 
 
 def main(argv=None):

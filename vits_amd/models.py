@@ -308,6 +308,61 @@ class Generator(nn.Module):
         return self.forward(x, g)
 
 
+def _control_buffers(static, batch, t_x, dev):
+    """The static control buffers of a captured infer_bucketed(control=...),
+    neutral (every token free, scale 1, no target); returns the control dict
+    of views the capture hands to infer_bucketed."""
+    static["given"] = torch.full((batch, t_x), -1, device=dev, dtype=torch.int32)
+    static["tok_scale"] = torch.ones(batch, t_x, device=dev, dtype=torch.float32)
+    static["target"] = torch.zeros(batch, device=dev, dtype=torch.int32)
+    static["ctl_neutral"] = True
+    return {k: static[k] for k in ("given", "tok_scale", "target")}
+
+
+def _control_fill(static, rows, batch, t_x):
+    """Write one replay's controls into the static buffers with one upload
+    each: ``rows`` = per row None or dict(given=, tok_scale=, target=) whose
+    entries may be None; tokens past a row's values and rows past ``rows``
+    stay neutral (-1 / 1.0 / 0).  A device tensor as ``given`` is copied
+    device to device (no host visit)."""
+    if not any(v is not None for row in rows for v in (row or {}).values()):
+        # no control in this replay: nothing is uploaded; buffers that still
+        # hold an earlier replay's controls are reset on the device
+        if not static["ctl_neutral"]:
+            static["given"].fill_(-1)
+            static["tok_scale"].fill_(1.0)
+            static["target"].zero_()
+            static["ctl_neutral"] = True
+        return
+    static["ctl_neutral"] = False
+    given = torch.full((batch, t_x), -1, dtype=torch.int32)
+    scale = torch.ones(batch, t_x, dtype=torch.float32)
+    target = torch.zeros(batch, dtype=torch.int32)
+    late = []
+    for i, row in enumerate(rows):
+        row = row or {}
+        unknown = set(row) - {"given", "tok_scale", "target"}
+        if unknown:
+            raise ValueError(f"replay: unknown control(s) {sorted(unknown)}")
+        g, sc, tg = row.get("given"), row.get("tok_scale"), row.get("target")
+        for name, v in (("given", g), ("tok_scale", sc)):
+            if v is not None and len(v) > t_x:
+                raise ValueError(f"replay: {len(v)} values of {name} do not fit {t_x} tokens")
+        if isinstance(g, torch.Tensor) and g.is_cuda:
+            late.append((i, g))
+        elif g is not None:
+            given[i, :len(g)] = torch.as_tensor(g, dtype=torch.int32)
+        if sc is not None:
+            scale[i, :len(sc)] = torch.as_tensor(sc, dtype=torch.float32).cpu()
+        if tg is not None:
+            target[i] = int(tg)
+    static["given"].copy_(given)
+    static["tok_scale"].copy_(scale)
+    static["target"].copy_(target)
+    for i, g in late:
+        static["given"][i, :g.numel()].copy_(g.reshape(-1).to(torch.int32))
+
+
 class SynthesizerTrn(nn.Module):
     """Synthesizer for training and inference (models.py:411-575)."""
 
@@ -463,6 +518,26 @@ class SynthesizerTrn(nn.Module):
         return self.infer_p2(attn, m_p, s_p, g, noise * noise_scale)
 
     @torch.no_grad()
+    def infer_durations(self, x, emo, sid, durations, noise):
+        """``infer`` with the durations given instead of predicted: infer_p1,
+        commons.infer_path(durations), infer_p2, the way the reference's
+        infer_p2(attn, ...) is driven with a hand-made path.  B = 1, exact
+        lengths, eager.  ``durations``: [t_x] (or [1, 1, t_x]) frames per
+        token, integers >= 0 (a token of 0 frames gets none); ``noise`` [1, C,
+        y_len], y_len = max(sum(durations), 1), pre-scaled like infer_p2's.
+        This is the definition infer_bucketed(control=...) is held to, bit for
+        bit."""
+        assert x.size(0) == 1
+        m_p, s_p, _, g = self.infer_p1(x, emo, sid)
+        d = torch.as_tensor(durations, device=x.device).reshape(1, 1, -1).to(torch.float32)
+        if d.shape[-1] != x.size(1) or bool((d < 0).any()):
+            raise ValueError(f"infer_durations: need {x.size(1)} durations >= 0, got "
+                             f"{tuple(d.shape)}")
+        y_len = max(int(d.sum().item()), 1)
+        attn = commons.infer_path(d, x.size(1), y_len, dtype=torch.float32)
+        return self.infer_p2(attn, m_p, s_p, g, noise)
+
+    @torch.no_grad()
     def infer_p1(self, x, emo, sid):
         """Text side (models.py:558-566): returns m_p, s_p = exp(logs_p), logw, g."""
         assert x.size(0) == 1
@@ -498,7 +573,7 @@ class SynthesizerTrn(nn.Module):
 
     @torch.no_grad()
     def infer_bucketed(self, x, emo, sid, noise, t_y, *, x_lengths=None, length_scale=1.0,
-                       noise_start=None, n_rows=None):
+                       noise_start=None, n_rows=None, control=None):
         """infer (models.py:537-556) / EmoVITS.infer (infer.py:160-182) with
         NO host synchronisation, over a static bucket of t_y frames - the
         whole utterance can be captured into one hipGraph
@@ -534,7 +609,17 @@ class SynthesizerTrn(nn.Module):
         ``length_scale``: a number, or a contiguous fp32 [B] device tensor
         of per-row speeds read on the device (ops.expand_durations'
         ``rate``): row b is then what the call with float(length_scale[b])
-        computes, and a captured graph serves every mix of speeds."""
+        computes, and a captured graph serves every mix of speeds.
+
+        ``control`` = dict(given=, tok_scale=, target=) of device tensors
+        (int32 [B, t_x], fp32 [B, t_x], int32 [B]; each may be None or left
+        out): the durations come from ops.duration_plan (pinned tokens,
+        per-token scales, a total to fit; ``length_scale`` is its rate) and the
+        start draw and the expansion read them (their ``durations=`` forms).
+        The call then additionally returns (dur int32 [B, t_x], plan_meta
+        int32 [2, B] = total | status) as its last two values; each row is bit
+        for bit infer_durations of its returned durations.  None: nothing
+        changes and no further kernel is launched."""
         engine._check_gpu(x, "SynthesizerTrn.infer_bucketed")
         rate = length_scale if isinstance(length_scale, torch.Tensor) else float(length_scale)
         dt = x.dtype
@@ -552,28 +637,42 @@ class SynthesizerTrn(nn.Module):
             logw = engine.get_plan(self.dp, engine.DurationPlan).run(h, g, lengths=xl)
             m_p, s_p, logw = m_p.to(dt), s_p.to(dt), logw.to(dt)
         starts = None
+        # how the durations reach the draw and the expansion: the predictor's
+        # logw with the speed, or the plan's integers
+        src = dict(rate=rate, half_round=dt == torch.float16)
+        plan = ()
+        if control is not None:
+            unknown = set(control) - {"given", "tok_scale", "target"}
+            if unknown:
+                raise ValueError(f"infer_bucketed: unknown control(s) {sorted(unknown)}")
+            plan_meta = torch.empty(2, x.shape[0], device=x.device, dtype=torch.int32)
+            dur = engine.ops.duration_plan(
+                logw, rate=rate, x_len=xl, half_round=dt == torch.float16,
+                given=control.get("given"), tok_scale=control.get("tok_scale"),
+                target=control.get("target"), meta=plan_meta)[0]
+            src = dict(durations=dur)
+            plan = (dur, plan_meta)
         if shared_pool:
             starts, y_len, status, used_total = engine.ops.draw_starts(
-                logw, m_p.shape[1], noise.numel(), noise_start, rate=rate,
-                x_len=xl, half_round=dt == torch.float16, n_rows=n_rows)
+                logw, m_p.shape[1], noise.numel(), noise_start, x_len=xl, n_rows=n_rows, **src)
             noise_start = None
         z, lens = engine.ops.expand_durations(
-            logw, m_p, s_p, noise, int(t_y), rate=rate, x_len=xl,
-            noise_start=noise_start, half_round=dt == torch.float16,
-            stage_mult=self._stage_mult(), starts=starts)
+            logw, m_p, s_p, noise, int(t_y), x_len=xl, noise_start=noise_start,
+            stage_mult=self._stage_mult(), starts=starts, **src)
         gf = engine._f32(g)
         with engine.ops.length_skip(64):
             engine.get_plan(self.flow, engine.CouplingFlowPlan).run_(z, gf, lengths=lens[0])
             o = engine.get_plan(self.dec, engine.GeneratorPlan).run(z, gf, lengths=lens[1:])
         if shared_pool:
-            return o.to(m_p.dtype), y_len, status, used_total
+            return (o.to(m_p.dtype), y_len, status, used_total) + plan
         if noise_start is not None:
-            return o.to(m_p.dtype), lens[0::len(lens) - 1]
-        return o.to(m_p.dtype), lens[0]
+            return (o.to(m_p.dtype), lens[0::len(lens) - 1]) + plan
+        return (o.to(m_p.dtype), lens[0]) + plan
 
     @torch.no_grad()
     def capture_infer_bucketed(self, t_x, t_y, *, noise_len=None, padded_text=False,
-                               length_scale=1.0, warmup=2, batch=1, pool_len=None):
+                               length_scale=1.0, warmup=2, batch=1, pool_len=None,
+                               control=False):
         """One hipGraph for a whole utterance (infer_bucketed) of t_x tokens
         (padded_text: up to t_x, x_lengths given at replay) into a t_y-frame
         bucket.  noise_len: replay reads a flat noise buffer of that many
@@ -596,10 +695,23 @@ class SynthesizerTrn(nn.Module):
         speeds) captures a rate-free graph: the speeds live in the static
         buffer ``rates`` and replay takes them per call, batch > 1 as
         run(..., rates=[n floats]) (padding rows get 1.0), batch 1 as
-        run(..., rate=float); without them the buffer keeps what it holds."""
+        run(..., rate=float); without them the buffer keeps what it holds.
+
+        ``control=True`` captures infer_bucketed(control=...) over the static
+        buffers ``given`` (int32 [batch, t_x]), ``tok_scale`` (fp32 [batch,
+        t_x]) and ``target`` (int32 [batch]); the graph is always rate-free
+        (a number as ``length_scale`` is the initial speed of every row).
+        Replay takes them per call as run(..., control=dict(given=,
+        tok_scale=, target=)): batch 1 one row each (sequences of up to t_x
+        values, an int), batch > 1 lists with one entry per row; a missing or
+        None entry, the tokens past a row's values and padding rows get -1 /
+        1.0 / 0 (free, unscaled, no target), so does a replay without
+        ``control``.  The outputs gain (dur, plan_meta) as their last two."""
+        if control and not isinstance(length_scale, torch.Tensor):
+            length_scale = torch.full((int(batch),), float(length_scale))
         if batch > 1:
             return self._capture_infer_batch(t_x, t_y, int(batch), noise_len, padded_text,
-                                             length_scale, warmup, pool_len)
+                                             length_scale, warmup, pool_len, control)
         dev = next(self.parameters()).device
         dt = next(self.parameters()).dtype
         C = self.inter_channels
@@ -611,13 +723,15 @@ class SynthesizerTrn(nn.Module):
                       noise=torch.zeros(noise_len if noise_len else C * t_y, device=dev))
         if isinstance(length_scale, torch.Tensor):
             static["rates"] = length_scale.to(device=dev, dtype=torch.float32).reshape(1).clone()
+        ctl = _control_buffers(static, 1, t_x, dev) if control else None
 
         def body():
             noise = static["noise"] if noise_len else static["noise"].view(1, C, t_y)
             return self.infer_bucketed(static["x"], static["emo"], static["sid"], noise, t_y,
                                        x_lengths=static["xl"] if padded_text else None,
                                        length_scale=static.get("rates", length_scale),
-                                       noise_start=static["start"] if noise_len else None)
+                                       noise_start=static["start"] if noise_len else None,
+                                       control=ctl)
 
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
@@ -629,7 +743,12 @@ class SynthesizerTrn(nn.Module):
         with torch.cuda.graph(graph):
             out = body()
 
-        def run(x, emo, sid, noise=None, noise_start=None, x_length=None, rate=None):
+        def run(x, emo, sid, noise=None, noise_start=None, x_length=None, rate=None,
+                control=None):
+            if ctl is not None:
+                _control_fill(static, [control], 1, t_x)
+            elif control is not None:
+                raise ValueError("replay: this graph was captured without control")
             if rate is not None:
                 if "rates" not in static:
                     raise ValueError("replay: this graph was captured at a fixed length_scale")
@@ -656,7 +775,7 @@ class SynthesizerTrn(nn.Module):
         return run
 
     def _capture_infer_batch(self, t_x, t_y, batch, noise_len, padded_text, length_scale, warmup,
-                             pool_len):
+                             pool_len, control=False):
         """capture_infer_bucketed for batch > 1 (see there)."""
         if not padded_text or not noise_len:
             raise ValueError("capture_infer_bucketed: batch > 1 needs padded_text=True and noise_len")
@@ -674,12 +793,14 @@ class SynthesizerTrn(nn.Module):
             static["rates"] = length_scale.to(device=dev, dtype=torch.float32).reshape(
                 batch).clone()
         cols = torch.arange(t_x, device=dev).view(1, t_x, 1)
+        ctl = _control_buffers(static, batch, t_x, dev) if control else None
 
         def body():
             return self.infer_bucketed(static["x"], static["emo"], static["sid"], static["noise"],
                                        t_y, x_lengths=static["xl"],
                                        length_scale=static.get("rates", length_scale),
-                                       noise_start=static["pool"], n_rows=static["n_rows"])
+                                       noise_start=static["pool"], n_rows=static["n_rows"],
+                                       control=ctl)
 
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
@@ -691,8 +812,18 @@ class SynthesizerTrn(nn.Module):
         with torch.cuda.graph(graph):
             out = body()
 
-        def run(x, emo, sid, x_lengths, pool, n_rows=None, rates=None):
+        def run(x, emo, sid, x_lengths, pool, n_rows=None, rates=None, control=None):
             n = x.shape[0] if n_rows is None else int(n_rows)
+            if ctl is not None:
+                for k, v in (control or {}).items():
+                    if v is not None and len(v) != n:
+                        raise ValueError(f"batched replay: {n} rows need {n} entries of "
+                                         f"control {k!r}, got {len(v)}")
+                rows = [{k: (v[i] if v is not None else None) for k, v in (control or {}).items()}
+                        for i in range(n)]
+                _control_fill(static, rows, batch, t_x)
+            elif control is not None:
+                raise ValueError("batched replay: this graph was captured without control")
             if rates is not None:
                 if "rates" not in static:
                     raise ValueError("batched replay: this graph was captured at a fixed "

@@ -1059,13 +1059,94 @@ def _rate_arg(rate, B: int, what: str):
     return float(rate), None
 
 
+def _durations_arg(durations, B: int, t_x: int, rate, half_round, what: str):
+    """``durations`` of expand_durations / draw_starts: an int32 [B, t_x]
+    device tensor whose rows are contiguous; it replaces logw, rate and
+    half_round, so a non-default one of those next to it is an error."""
+    if isinstance(rate, torch.Tensor) or rate != 1.0 or half_round:
+        raise _lib.VitsAmdError(f"{what}: durations already hold the speed and the rounding; "
+                                "give durations or rate / half_round, not both")
+    if (not isinstance(durations, torch.Tensor) or durations.dtype != torch.int32
+            or tuple(durations.shape) != (B, t_x) or durations.stride(1) != 1
+            or durations.stride(0) < t_x):
+        raise _lib.VitsAmdError(f"{what}: durations must be an int32 [{B}, {t_x}] tensor with "
+                                "contiguous rows")
+    require_device(durations)
+    return durations
+
+
+def duration_plan(logw: torch.Tensor, *, rate=1.0, x_len: Optional[torch.Tensor] = None,
+                  half_round: bool = False, given: Optional[torch.Tensor] = None,
+                  tok_scale: Optional[torch.Tensor] = None,
+                  target: Optional[torch.Tensor] = None, w_out=False,
+                  dur: Optional[torch.Tensor] = None, meta: Optional[torch.Tensor] = None):
+    """The integer durations of every token under a caller's controls, on the
+    device with no host sync (vits_duration_plan, include/vits_amd.h has the
+    arithmetic).  ``logw`` [B, t_x] or [B, 1, t_x] (rows may be strided);
+    ``rate`` as in expand_durations; ``given`` int32 [B, t_x]: >= 0 pins a
+    token to that many frames (0 allowed), < 0 leaves it free; ``tok_scale``
+    fp32 [B, t_x]: a per-token factor (>= 0) on the free tokens; ``target``
+    int32 [B]: > 0 = the row lasts exactly that many frames (the free tokens
+    are fitted, ``rate`` is not applied), <= 0 = none.  Returns (dur int32 [B,
+    t_x] (0 at and past x_len), total int32 [B], status int32 [B]) and, with
+    ``w_out`` (True, or an fp32 [B, t_x] tensor to fill), the w behind every
+    free token's duration.  status 1: the target cannot be met and the row
+    holds the no-target durations.  total and status are views of ``meta``
+    (int32 [2, B]).  ``dur`` feeds ``expand_durations(durations=)`` and
+    ``draw_starts(durations=)``."""
+    require_device(logw)
+    B = logw.shape[0]
+    if logw.dim() == 3:
+        logw = logw.reshape(B, -1)
+    if logw.dim() != 2 or logw.dtype != torch.float32 or logw.stride(1) != 1:
+        logw = logw.reshape(B, -1).float().contiguous()
+    t_x = logw.shape[1]
+    rate, rates = _rate_arg(rate, B, "duration_plan")
+    dev = logw.device
+
+    def opt(t, dtype, shape, name):
+        if t is None:
+            return None
+        if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape
+                or not t.is_contiguous()):
+            raise _lib.VitsAmdError(f"duration_plan: {name} must be a contiguous {dtype} "
+                                    f"{list(shape)} tensor")
+        require_device(t)
+        return t
+
+    given = opt(given, torch.int32, (B, t_x), "given")
+    tok_scale = opt(tok_scale, torch.float32, (B, t_x), "tok_scale")
+    target = opt(target, torch.int32, (B,), "target")
+    x_len = opt(x_len, torch.int32, (B,), "x_len")
+    if dur is None:
+        dur = torch.empty(B, t_x, device=dev, dtype=torch.int32)
+    if meta is None:
+        meta = torch.empty(2, B, device=dev, dtype=torch.int32)
+    opt(dur, torch.int32, (B, t_x), "dur")
+    opt(meta, torch.int32, (2, B), "meta")
+    w = None
+    if w_out is True:
+        w = torch.empty(B, t_x, device=dev, dtype=torch.float32)
+    elif w_out is not False and w_out is not None:
+        w = opt(w_out, torch.float32, (B, t_x), "w_out")
+    check(_lib.load().vits_duration_plan(
+        logw.data_ptr(), logw.stride(0), _ptr(x_len), t_x,
+        1.0 if rates is not None else rate, _ptr(rates), int(half_round), _ptr(given),
+        _ptr(tok_scale), _ptr(target), dur.data_ptr(), meta.data_ptr(), _ptr(w), B,
+        _stream_ptr(dev)), "vits_duration_plan")
+    if w is not None:
+        return dur, meta[0], meta[1], w
+    return dur, meta[0], meta[1]
+
+
 def expand_durations(logw: torch.Tensor, m_p: torch.Tensor, s_p: torch.Tensor,
                      noise: torch.Tensor, t_y: int, *, rate=1.0,
                      noise_scale: float = 1.0, x_len: Optional[torch.Tensor] = None,
                      noise_start: Optional[torch.Tensor] = None, half_round: bool = False,
                      stage_mult=(1,), out: Optional[torch.Tensor] = None,
                      lens: Optional[torch.Tensor] = None,
-                     starts: Optional[torch.Tensor] = None):
+                     starts: Optional[torch.Tensor] = None,
+                     durations: Optional[torch.Tensor] = None):
     """Durations -> (z [B, C, t_y], lens int32 [n_stage, B]) on the device,
     without the host sync of models.py:547 / infer.py:171: w_ceil =
     ceil(exp(logw) * rate), y_len = max(sum, 1), z = the one-hot expansion of
@@ -1082,9 +1163,20 @@ def expand_durations(logw: torch.Tensor, m_p: torch.Tensor, s_p: torch.Tensor,
     ``noise_start``: the flat buffer read at those explicit starts (a
     negative one: z = 0, nothing read); ``lens`` stays [n_stage, B].
     ``rate``: a number, or a contiguous fp32 [B] device tensor of per-row
-    speeds (row b is then bit for bit the call with ``rate=float(rate[b])``)."""
-    rate, rates = _rate_arg(rate, m_p.shape[0], "expand_durations")
-    require_device(logw, m_p, s_p, noise)
+    speeds (row b is then bit for bit the call with ``rate=float(rate[b])``).
+    ``durations`` (int32 [B, t_x] device tensor, e.g. ``duration_plan``'s):
+    the integer durations themselves in place of ceil(exp(logw) * rate)
+    (vits_expand_durations_int: a token of 0 frames gets none, y_len = max(sum,
+    1) as a plain integer sum); ``logw`` may then be None, and ``rate`` and
+    ``half_round`` must be left at their defaults."""
+    if durations is not None:
+        durations = _durations_arg(durations, m_p.shape[0], m_p.shape[2], rate, half_round,
+                                   "expand_durations")
+        rate, rates = None, None
+        require_device(m_p, s_p, noise)
+    else:
+        rate, rates = _rate_arg(rate, m_p.shape[0], "expand_durations")
+        require_device(logw, m_p, s_p, noise)
     if starts is not None:
         if noise_start is not None:
             raise _lib.VitsAmdError("expand_durations: give noise_start or starts, not both")
@@ -1093,7 +1185,8 @@ def expand_durations(logw: torch.Tensor, m_p: torch.Tensor, s_p: torch.Tensor,
                 or not starts.is_contiguous()):
             raise _lib.VitsAmdError(f"expand_durations: starts must be int64 [{m_p.shape[0]}]")
     B, C_, t_x = m_p.shape
-    logw = logw.reshape(B, t_x).float().contiguous()
+    if durations is None:
+        logw = logw.reshape(B, t_x).float().contiguous()
     m_p = m_p.float().contiguous()
     s_p = s_p.float().contiguous()
     noise = noise.float().contiguous()
@@ -1117,6 +1210,14 @@ def expand_durations(logw: torch.Tensor, m_p: torch.Tensor, s_p: torch.Tensor,
     else:
         mode, start_ptr = 1, noise_start.data_ptr()
     lib = _lib.load()
+    if durations is not None:
+        check(lib.vits_expand_durations_int(
+            durations.data_ptr(), durations.stride(0), _ptr(x_len), t_x,
+            m_p.data_ptr(), s_p.data_ptr(), m_p.stride(0), m_p.stride(1), noise.data_ptr(),
+            mode, start_ptr, noise.numel(), float(noise_scale), out.data_ptr(),
+            B, C_, t_y, lens.data_ptr(), mult, n_stage, _stream_ptr(m_p.device)),
+            "vits_expand_durations_int")
+        return out, lens
     fn, what = ((lib.vits_expand_durations, "vits_expand_durations") if rates is None else
                 (lib.vits_expand_durations_rows, "vits_expand_durations_rows"))
     check(fn(
@@ -1148,7 +1249,8 @@ def _n_rows_ptr(n_rows, B: int, device, what: str):
 def draw_starts(logw: torch.Tensor, channels: int, noise_len: int, pool: torch.Tensor, *,
                 rate=1.0, x_len: Optional[torch.Tensor] = None,
                 half_round: bool = False, n_rows=None, starts: Optional[torch.Tensor] = None,
-                meta: Optional[torch.Tensor] = None):
+                meta: Optional[torch.Tensor] = None,
+                durations: Optional[torch.Tensor] = None):
     """The noise-slice starts of B utterances as B consecutive EmoVITS.infer
     calls would draw them (infer.py:173): y_len[b] from ``logw`` with
     expand_durations' arithmetic, then np.random.randint(noise_len - channels
@@ -1161,18 +1263,30 @@ def draw_starts(logw: torch.Tensor, channels: int, noise_len: int, pool: torch.T
     both.  Rows at or past ``n_rows`` (None, int or int32 [1] device tensor)
     draw nothing.  When everything is >= 0, ``numpy_draw_commit(state,
     used_total)`` leaves numpy's generator where the B calls would.
-    ``rate``: a number or an fp32 [B] device tensor, as in expand_durations."""
-    B = logw.shape[0]
-    rate, rates = _rate_arg(rate, B, "draw_starts")
-    require_device(logw, pool)
-    logw = logw.reshape(B, -1).float().contiguous()
-    t_x = logw.shape[1]
+    ``rate``: a number or an fp32 [B] device tensor, as in expand_durations.
+    ``durations`` (int32 [B, t_x] device tensor): y_len[b] = max(sum of row b,
+    1) from the integer durations themselves (vits_draw_starts_int); ``logw``
+    may then be None, ``rate`` and ``half_round`` stay at their defaults."""
+    if durations is not None:
+        if durations.dim() != 2:
+            raise _lib.VitsAmdError("draw_starts: durations must be an int32 [B, t_x] tensor")
+        B, t_x = durations.shape
+        durations = _durations_arg(durations, B, t_x, rate, half_round, "draw_starts")
+        rate, rates = None, None
+        require_device(pool)
+    else:
+        B = logw.shape[0]
+        rate, rates = _rate_arg(rate, B, "draw_starts")
+        require_device(logw, pool)
+        logw = logw.reshape(B, -1).float().contiguous()
+        t_x = logw.shape[1]
     if pool.dtype != torch.int32 or pool.dim() != 1 or not pool.is_contiguous() or not pool.numel():
         raise _lib.VitsAmdError("draw_starts: pool must be a contiguous int32 [P] tensor, P >= 1")
+    dev = pool.device
     if starts is None:
-        starts = torch.empty(B, device=logw.device, dtype=torch.int64)
+        starts = torch.empty(B, device=dev, dtype=torch.int64)
     if meta is None:
-        meta = torch.empty(2 * B + 1, device=logw.device, dtype=torch.int32)
+        meta = torch.empty(2 * B + 1, device=dev, dtype=torch.int32)
     if (tuple(starts.shape) != (B,) or starts.dtype != torch.int64 or not starts.is_contiguous()
             or tuple(meta.shape) != (2 * B + 1,) or meta.dtype != torch.int32
             or not meta.is_contiguous()):
@@ -1180,8 +1294,14 @@ def draw_starts(logw: torch.Tensor, channels: int, noise_len: int, pool: torch.T
     if x_len is not None and (x_len.dtype != torch.int32 or tuple(x_len.shape) != (B,)
                               or not x_len.is_contiguous()):
         raise _lib.VitsAmdError(f"draw_starts: x_len must be a contiguous int32 [{B}] tensor")
-    keep, nr_ptr = _n_rows_ptr(n_rows, B, logw.device, "draw_starts")
+    keep, nr_ptr = _n_rows_ptr(n_rows, B, dev, "draw_starts")
     lib = _lib.load()
+    if durations is not None:
+        check(lib.vits_draw_starts_int(
+            durations.data_ptr(), durations.stride(0), _ptr(x_len), t_x,
+            int(channels), int(noise_len), pool.data_ptr(), pool.numel(), nr_ptr, B,
+            starts.data_ptr(), meta.data_ptr(), _stream_ptr(dev)), "vits_draw_starts_int")
+        return starts, meta[:B], meta[B:2 * B], meta[2 * B:]
     fn, what = ((lib.vits_draw_starts, "vits_draw_starts") if rates is None else
                 (lib.vits_draw_starts_rows, "vits_draw_starts_rows"))
     check(fn(

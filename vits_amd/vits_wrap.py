@@ -127,11 +127,68 @@ class VITSWrap(object):
             i += 1
         return out_id, out_txt
 
+    def _duration_controls(self, inputs, n_segments, what):
+        """The duration controls of a request: None, or the keyword arguments
+        of EmoVITS.infer / infer_pcm.  ``durations`` (frames per token of the
+        front end's vector sequence, < 0: predicted), ``token_scale`` (a
+        factor per token), ``duration_s`` (the utterance lasts round(s * rate
+        / hop) frames of the model, before the output stage).  They address
+        the tokens of ONE segment: text that _split_utt_text cuts is refused,
+        as in ``aligning``."""
+        d, s, sec = inputs.get("durations"), inputs.get("token_scale"), inputs.get("duration_s")
+        if d is None and s is None and sec is None:
+            return None
+        if n_segments != 1:
+            raise ValueError(f"{what}: the text splits into {n_segments} segments of at most "
+                             f"{self.max_utt_length} characters; duration controls address the "
+                             "tokens of one segment")
+        target = None
+        if sec is not None:
+            sec = float(sec)
+            sp = self.speecher
+            if not np.isfinite(sec) or sec <= 0:
+                raise ValueError(f"{what}: duration_s must be a positive number, got {sec}")
+            target = int(round(sec * sp.sampling_rate / sp.hop_size))
+            if target < 1:
+                raise ValueError(f"{what}: duration_s = {sec} is less than one frame")
+        return dict(durations=d, token_scale=s, target_frames=target, return_durations=True)
+
+    def _with_durations(self, out, durations):
+        sp = self.speecher
+        out["durations"] = durations
+        out["boundaries_s"] = (np.concatenate([[0], np.cumsum(durations, dtype=np.int64)])
+                               * (sp.hop_size / sp.sampling_rate))
+        return out
+
     @torch.no_grad()
     def speaking(self, inputs: dict) -> dict:
+        """One synthesis request (vits_wrap.py:168-218).  ``durations`` /
+        ``token_scale`` / ``duration_s`` in the request (see
+        _duration_controls) control the timing of a one-segment text;
+        the result then also holds ``durations`` (int32 [Tx], the frames per
+        token that were spoken) and ``boundaries_s`` (float64 [Tx + 1], at the
+        model's rate, before pitch and rate changes)."""
         inputs, utt_id, utt_text, spkid, volume, speed, pitch, sampling_rate, tail_silence, emotion = \
             self._parse_input(inputs)
         ids, texts = self._split_utt_text(utt_id, utt_text)
+        ctl = self._duration_controls(inputs, len(texts), "speaking")
+        if ctl is not None:
+            t0 = time.time()
+            _, segtext, vec = self.textparser(ids[0], texts[0])
+            t1 = time.time()
+            if self.device_post:
+                wav, emotion, n_model, dur = self.speecher.infer_pcm(
+                    spkid, vec, emotion, duration_rate=speed, pitch=pitch,
+                    sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence, **ctl)
+            else:
+                wav, emotion, dur = self.speecher.infer(spkid, vec, emotion, duration_rate=speed,
+                                                        **ctl)
+                n_model = len(wav)
+                wav = host_pcm(wav, self.default_sampling_rate, pitch, sampling_rate, volume,
+                               tail_silence)
+            out = self._finish(inputs, texts, [segtext], [len(wav)], [wav], n_model,
+                               sampling_rate, t1 - t0, time.time() - t1)
+            return self._with_durations(out, dur)
         batch_wav, batch_wavlen = [], 0
         segtexts, seg_samples = [], []  # per segment: front-end text, PCM samples (tail included)
         t_front, t_back = 0.0, 0.0
@@ -229,6 +286,40 @@ class VITSWrap(object):
         return out
 
     @torch.no_grad()
+    def speaking_like(self, inputs: dict) -> dict:
+        """``text`` in the voice of ``spkid`` with the timing of a recording:
+        {"wav", "sampling_rate_in", "spkid_src", "text"} as ``aligning`` takes
+        them (spkid_src: the recording's speaker) plus the fields of
+        ``speaking`` for the target voice.  One alignment graph replay whose
+        durations go device to device into the controlled synthesis graph,
+        then that replay (EmoVITS.infer_pcm_like): the result of ``aligning``
+        followed by ``speaking`` with its durations, byte for byte, without
+        the durations visiting the host in between.  One-segment text only;
+        needs device_post=True on a ROCm GPU."""
+        if not self.device_post:
+            raise ValueError("VITSWrap.speaking_like needs device_post=True on a ROCm GPU")
+        inputs, utt_id, utt_text, spkid, volume, speed, pitch, sampling_rate, tail_silence, emotion = \
+            self._parse_input(inputs)
+        ids, texts = self._split_utt_text(utt_id, utt_text)
+        if len(texts) != 1:
+            raise ValueError(f"speaking_like: the text splits into {len(texts)} segments of at "
+                             f"most {self.max_utt_length} characters; one segment per recording")
+        if "spkid_src" not in inputs or "wav" not in inputs:
+            raise ValueError("speaking_like needs the recording (wav) and its speaker (spkid_src)")
+        rec = inputs.pop("wav")
+        t0 = time.time()
+        _, segtext, vec = self.textparser(ids[0], texts[0])
+        t1 = time.time()
+        wav, emotion, n_model, dur = self.speecher.infer_pcm_like(
+            rec, int(inputs["spkid_src"]), spkid, vec, emotion,
+            sampling_rate_in=inputs.get("sampling_rate_in"), pitch=pitch,
+            sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence,
+            return_durations=True)
+        out = self._finish(inputs, texts, [segtext], [len(wav)], [wav], n_model, sampling_rate,
+                           t1 - t0, time.time() - t1)
+        return self._with_durations(out, dur)
+
+    @torch.no_grad()
     def aligning(self, inputs: dict) -> dict:
         """Forced-alignment request: {"wav" (int16 or float samples), "text",
         "spkid", "emotion", "sampling_rate_in", "id"} -> the same dict plus
@@ -283,6 +374,10 @@ class VITSWrap(object):
         call (see infer_pcm_requests); with explicit emotions numpy's
         generator ends where the loop leaves it.  Otherwise: the loop."""
         list_of_inputs = list(list_of_inputs)
+        if any(i.get(k) is not None for i in list_of_inputs
+               for k in ("durations", "token_scale", "duration_s")):
+            # a request with duration controls: the loop (speaking serves it)
+            return [self.speaking(inputs) for inputs in list_of_inputs]
         parsed = [self._parse_input(inputs) for inputs in list_of_inputs] \
             if self.batch_segments else []
         split = [self._split_utt_text(p[1], p[2]) for p in parsed]
