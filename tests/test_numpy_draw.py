@@ -55,7 +55,7 @@ def test_device_draw_rejects_slices_that_do_not_fit():
 
 
 def _host_draw(high: int, n: int):
-    """infer.py EmoVITS._infer_graph's draw protocol (vits_amd/infer.py:200-214)
+    """The draw protocol of EmoVITS._infer_graph (vits_amd/infer.py), restated
     with a pool of ``n`` words: -2 (all rejected) advances numpy's generator
     past the pool and draws again from the next words."""
     while True:

@@ -13,7 +13,7 @@ from __future__ import annotations
 import os
 import sys
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -38,6 +38,16 @@ class PcmRequest:
     durations: Optional[Sequence] = None
     token_scale: Optional[Sequence] = None
     target_frames: Optional[Sequence] = None
+
+
+class _Output(NamedTuple):
+    """The output controls of one call or row, resolved (EmoVITS._output)."""
+    pitch: float
+    sampling_rate: int  # (the model's when the caller gave None)
+    volume: float
+    tail_silence: float
+    tail: int  # tail silence in samples at sampling_rate
+    passes: list  # (up, down) resampling passes (EmoVITS._post_passes)
 
 
 class EmoVITS(object):
@@ -161,13 +171,32 @@ class EmoVITS(object):
         t_x = text_t.shape[1]
         if self.graph_cache <= 0:
             return self.model.infer_p1(text_t, emo, sid)
-        run = self._p1_graphs.pop(t_x, None)
-        if run is None:
-            run = self.model.capture_infer_p1(t_x)
-            while len(self._p1_graphs) >= self.graph_cache:
-                self._p1_graphs.pop(next(iter(self._p1_graphs)))
-        self._p1_graphs[t_x] = run  # most recently used last
+        run = self._cached_graph(t_x, lambda: self.model.capture_infer_p1(t_x), p1=True)
         return tuple(t.clone() for t in run(text_t, emo, sid))
+
+    def _cached_graph(self, key, capture, p1=False):
+        """The graph cached under ``key`` in self._graphs (at most
+        ``max_graphs``; p1: in self._p1_graphs, at most ``graph_cache``),
+        most recently used last.  A miss evicts the least recently used
+        entries while the cache is full, then keeps what ``capture()``
+        returns."""
+        cache, limit = ((self._p1_graphs, self.graph_cache) if p1
+                        else (self._graphs, self.max_graphs))
+        run = cache.pop(key, None)
+        if run is None:
+            while len(cache) >= limit:
+                cache.pop(next(iter(cache)))
+            run = capture()
+        cache[key] = run  # most recently used last
+        return run
+
+    def _capture_synthesis(self, xb, tyb, **kw):
+        """A whole-utterance graph (capture_infer_bucketed over padded text)
+        that reads this object's noise buffer."""
+        run = self.model.capture_infer_bucketed(xb, tyb, noise_len=self.noise.numel(),
+                                                padded_text=True, **kw)
+        run.static["noise"].copy_(self.noise.float())
+        return run
 
     def _resolve(self, spkid, emo):
         """Speaker mapping and emotion lookup of infer (infer.py:135-158):
@@ -187,11 +216,8 @@ class EmoVITS(object):
         return spkid, emo.to(device=self.device, dtype=self.dtype)
 
     def _inputs(self, spkid, text, emo):
-        x_length = text.shape[0]
         spkid, emo = self._resolve(spkid, emo)
-        sid = torch.tensor([spkid], dtype=torch.long, device=self.device)
-        text_t = torch.from_numpy(np.ascontiguousarray(text)).to(self.dtype).to(
-            self.device).unsqueeze(0)
+        x_length, text_t, sid = self._one_tensors(spkid, np.ascontiguousarray(text))
         return x_length, text_t, emo, sid
 
     @staticmethod
@@ -282,10 +308,27 @@ class EmoVITS(object):
         passes = [ops.resample_ratio(o, t) for o, t in steps if o != t]
         return [(u, d) for u, d in passes if u != d]
 
-    def _post(self, wav, passes, volume, tail, *, lengths, length_scale=1):
-        """wav [B, cap] -> int16 [B, >= n_out + tail] on the current stream:
-        every pass but the last writes an fp32 intermediate and its length,
-        the last one (or pcm16 alone) the PCM, zero past its end."""
+    def _output(self, pitch, sampling_rate, volume, tail_silence):
+        """A call's output controls, resolved: the sampling rate (None: the
+        model's), the tail silence in samples and the resampling passes."""
+        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
+        tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
+        return _Output(pitch, sampling_rate, volume, tail_silence, tail,
+                       self._post_passes(pitch, sampling_rate))
+
+    @staticmethod
+    def _n_out(n, passes):
+        """Samples that n model samples come to after ``passes``."""
+        for up, down in passes:
+            n = ops.resample_out_len(n, up, down)
+        return n
+
+    def _post(self, wav, out, *, lengths, length_scale=1):
+        """wav [B, cap] -> int16 [B, >= n_out + tail] on the current stream
+        under the controls ``out`` (_output): every pass but the last writes
+        an fp32 intermediate and its length, the last one (or pcm16 alone)
+        the PCM, zero past its end."""
+        passes, volume, tail = out.passes, out.volume, out.tail
         B = wav.shape[0]
         cap = wav.shape[1] if isinstance(lengths, torch.Tensor) else int(lengths)
         x = wav
@@ -324,13 +367,12 @@ class EmoVITS(object):
         chain.  ``durations`` / ``token_scale`` / ``target_frames`` /
         ``return_durations`` as in infer (the durations are then a fourth
         result).  Returns (pcm int16 [n], emo, n_model_samples)."""
-        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
+        out = self._output(pitch, sampling_rate, volume, tail_silence)
         ctl = self._controls(text.shape[0], durations, token_scale, target_frames,
                              return_durations)  # (refuses before anything is uploaded)
         x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
         got = [] if return_durations else None
-        pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, duration_rate, pitch,
-                                     sampling_rate, volume, tail_silence, ctl, got)
+        pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, duration_rate, out, ctl, got)
         return (pcm, emo, n, got[0]) if return_durations else (pcm, emo, n)
 
     def infer_pcm_like(self, wav, spkid_src, spkid, text, emo, *, sampling_rate_in=None,
@@ -345,42 +387,38 @@ class EmoVITS(object):
         ``infer_pcm(durations=...)`` returns, sample for sample, with numpy's
         generator left in the same state.  The frame bucket comes from the
         recording's frame count, which the host knows.  Needs a ROCm GPU."""
-        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
+        out = self._output(pitch, sampling_rate, volume, tail_silence)
         text = np.ascontiguousarray(text)
         (dur, frames), = self._align_rows([wav], [spkid_src], [text], [emo], sampling_rate_in,
                                           0.0, device=True)
         x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
         got = [] if return_durations else None
-        pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, 1.0, pitch, sampling_rate,
-                                     volume, tail_silence, (dur, None, 0, int(frames)), got)
+        pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, 1.0, out,
+                                     (dur, None, 0, int(frames)), got)
         return (pcm, emo, n, got[0]) if return_durations else (pcm, emo, n)
 
-    def _infer_pcm_one(self, x_length, text_t, emo, sid, duration_rate, pitch, sampling_rate,
-                       volume, tail_silence, ctl=None, got=None):
-        tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
+    def _infer_pcm_one(self, x_length, text_t, emo, sid, duration_rate, out, ctl=None, got=None):
+        """One utterance under the output controls ``out`` (_output): (pcm
+        int16 [n] on the host, model samples)."""
         if self.device.type != "cuda":
             from . import vits_wrap
 
             wav = self._infer_one(x_length, text_t, emo, sid, duration_rate, ctl, got)
-            pcm = vits_wrap.host_pcm(wav, self.sampling_rate, pitch, sampling_rate, volume,
-                                     tail_silence)
+            pcm = vits_wrap.host_pcm(wav, self.sampling_rate, out.pitch, out.sampling_rate,
+                                     out.volume, out.tail_silence)
             return pcm, len(wav)
-        passes = self._post_passes(pitch, sampling_rate)
         if self.graph and x_length <= 4096:
             pcm, n = self._infer_graph(
                 text_t, emo, sid, duration_rate,
-                post=lambda wav, y_len: self._post(wav, passes, volume, tail, lengths=y_len,
+                post=lambda wav, y_len: self._post(wav, out, lengths=y_len,
                                                    length_scale=self.hop_size),
                 ctl=ctl, got=got)
             n *= self.hop_size
         else:
             wav = self._infer_eager(x_length, text_t, emo, sid, duration_rate, ctl, got)
             n = wav.shape[-1]
-            pcm = self._post(wav.reshape(1, -1), passes, volume, tail, lengths=n)
-        n_out = n
-        for up, down in passes:
-            n_out = ops.resample_out_len(n_out, up, down)
-        return pcm[0, :n_out + tail].cpu().numpy(), n
+            pcm = self._post(wav.reshape(1, -1), out, lengths=n)
+        return pcm[0, :self._n_out(n, out.passes) + out.tail].cpu().numpy(), n
 
     # -- batched serving: all segments of a request in one utterance graph --------
     MAX_BATCH = 16
@@ -431,12 +469,68 @@ class EmoVITS(object):
         return [self._controls(np.shape(items[i][1])[0], cols[0][i], cols[1][i], cols[2][i], want)
                 for i in range(n)]
 
+    def _one_by_one(self, spkids, texts, emos, rates, ctls, outs, want):
+        """The rows of a group that is not batched (a single row, a CPU
+        device, graph=False), one after another on infer's path, or on
+        infer_pcm's under ``outs`` (one _output per row; None: waveforms).
+        Returns the lists (samples, model samples or None, durations or None
+        without ``want``), one entry per row."""
+        res = []
+        for i, (spkid, text) in enumerate(zip(spkids, texts)):
+            x_length, text_t, sid = self._one_tensors(spkid, text)
+            got = [] if want else None
+            if outs is None:
+                pcm, n = self._infer_one(x_length, text_t, emos[i], sid, rates[i], ctls[i],
+                                         got), None
+            else:
+                pcm, n = self._infer_pcm_one(x_length, text_t, emos[i], sid, rates[i], outs[i],
+                                             ctls[i], got)
+            res.append((pcm, n, got[0] if want else None))
+        return [list(col) for col in zip(*res)]
+
+    # The packed buffer of a group: ONE int16 tensor that one device-to-host
+    # copy brings over.  In front of the samples stand the int32 words
+    #   [offsets (B + 1) | y_len (B) | status (B) | used_total (1) | extra]
+    # (extra: the durations [B, text bucket] of a controlled group, else
+    # nothing), rounded up to 16 bytes: _header int16 elements.  Behind them,
+    # row after row at a stride of (numel - header) / B, the rows' PCM, of
+    # which samples [header, header + offsets[n]) are the n rows back to back
+    # (ops.pack_pcm / pack_pcm_rows write the offsets and move the samples).
+    # _pack writes the words, _unpack copies and reads them; no other code
+    # knows the layout.
     @staticmethod
     def _header(B, extra=0):
-        """int16 elements in front of a packed group's samples: the int32
-        words [offsets (B + 1) | y_len, status, used_total (2 B + 1) | extra
-        (the durations of a controlled group)], rounded to 16 bytes."""
+        """int16 elements in front of a packed group's samples."""
         return -(-2 * (3 * B + 2 + extra) // 8) * 8
+
+    @classmethod
+    def _pack(cls, B, pack, words, extra=None):
+        """The packed buffer of a group: ``pack(header)`` -> the int16 buffer
+        with its offsets and samples in place (a pack kernel), then ``words``
+        = (y_len [B], status [B], used_total [1]) and ``extra`` (int32, or
+        None) behind the offsets."""
+        n_extra = 0 if extra is None else extra.numel()
+        out = pack(cls._header(B, n_extra))
+        torch.cat(words, out=out[2 * (B + 1):2 * (3 * B + 2)].view(torch.int32))
+        if n_extra:
+            out[2 * (3 * B + 2):2 * (3 * B + 2 + n_extra)].view(torch.int32).copy_(
+                extra.reshape(-1))
+        return out
+
+    def _unpack(self, packed, bb, n, n_extra=0):
+        """The first n rows of a packed buffer of batch bucket bb on the host,
+        after its ONE copy (_to_host; the padding rows hold nothing and stay
+        behind): (samples int16 [offsets[n]], offsets int32 [n + 1], y_len
+        list [n], status list [n], used_total, extra int32 [n_extra] or
+        None)."""
+        header = self._header(bb, n_extra)
+        row_cap = (packed.numel() - header) // bb
+        buf = self._to_host(packed[:header + n * row_cap])
+        w = buf[:2 * (3 * bb + 2 + n_extra)].view(np.int32)
+        offs = w[:n + 1]
+        y, status = w[bb + 1:bb + 1 + n].tolist(), w[2 * bb + 1:2 * bb + 1 + n].tolist()
+        return (buf[header:header + int(offs[n])], offs, y, status, int(w[3 * bb + 1]),
+                w[3 * bb + 2:] if n_extra else None)
 
     def infer_batch(self, items, *, duration_rate=1.0, durations=None, token_scale=None,
                     target_frames=None, return_durations=False):
@@ -459,20 +553,18 @@ class EmoVITS(object):
         out = []
         for lo, hi in self._groups(len(texts)):
             if hi - lo == 1 or not self._batchable(texts[lo:hi]):
-                for i in range(lo, hi):
-                    x_length, text_t, sid = self._one_tensors(spkids[i], texts[i])
-                    got = [] if return_durations else None
-                    wav = self._infer_one(x_length, text_t, emos[i], sid, duration_rate, ctls[i],
-                                          got)
-                    out.append((wav, emos[i]) + ((got[0],) if return_durations else ()))
-                continue
-            durs = []
-            wav, y = self._infer_graph_batch(texts[lo:hi], emos[lo:hi], spkids[lo:hi],
-                                             duration_rate, ctls=ctls[lo:hi], got=durs)
-            hop = self.hop_size
-            host = wav[:hi - lo, 0, :max(y) * hop].cpu()  # one copy for the group
-            out += [(host[i, :n * hop].float().numpy(), emos[lo + i])
-                    + ((durs[i],) if return_durations else ()) for i, n in enumerate(y)]
+                wavs, _, durs = self._one_by_one(
+                    spkids[lo:hi], texts[lo:hi], emos[lo:hi], [duration_rate] * (hi - lo),
+                    ctls[lo:hi], None, return_durations)
+            else:
+                durs = []
+                wav, y = self._infer_graph_batch(texts[lo:hi], emos[lo:hi], spkids[lo:hi],
+                                                 duration_rate, ctls=ctls[lo:hi], got=durs)
+                hop = self.hop_size
+                host = wav[:hi - lo, 0, :max(y) * hop].cpu()  # one copy for the group
+                wavs = [host[i, :n * hop].float().numpy() for i, n in enumerate(y)]
+            out += [(w, emos[lo + i]) + ((durs[i],) if return_durations else ())
+                    for i, w in enumerate(wavs)]
         return out
 
     def infer_pcm_batch(self, items, *, duration_rate=1.0, pitch=1.0, sampling_rate=None,
@@ -491,54 +583,42 @@ class EmoVITS(object):
         as in infer_batch; a controlled group's final durations ride in the
         same copy, behind the header words, and come back as a fifth result
         (a list of int32 arrays) with ``return_durations``."""
-        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
-        tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
+        out = self._output(pitch, sampling_rate, volume, tail_silence)
         items = list(items)
         ctls = self._item_controls(items, durations, token_scale, target_frames, return_durations)
         texts, spkids, emos = self._resolve_items(items)
         chunks, offsets, n_model, durs = [], [0], [], []
         for lo, hi in self._groups(len(texts)):
             if hi - lo == 1 or not self._batchable(texts[lo:hi]):
-                for i in range(lo, hi):
-                    x_length, text_t, sid = self._one_tensors(spkids[i], texts[i])
-                    got = [] if return_durations else None
-                    pcm, n = self._infer_pcm_one(x_length, text_t, emos[i], sid, duration_rate,
-                                                 pitch, sampling_rate, volume, tail_silence,
-                                                 ctls[i], got)
-                    chunks.append(pcm)
-                    offsets.append(offsets[-1] + len(pcm))
-                    n_model.append(n)
-                    durs += got or []
+                pcms, ns, ds = self._one_by_one(
+                    spkids[lo:hi], texts[lo:hi], emos[lo:hi], [duration_rate] * (hi - lo),
+                    ctls[lo:hi], [out] * (hi - lo), return_durations)
+                chunks += pcms
+                offsets += (offsets[-1] + np.cumsum([len(p) for p in pcms])).tolist()
+                n_model += ns
+                durs += ds
                 continue
-            passes = self._post_passes(pitch, sampling_rate)
             (pcm, offs), y = self._infer_graph_batch(
                 texts[lo:hi], emos[lo:hi], spkids[lo:hi], duration_rate,
-                post=lambda wav, y_len, n_rows, words, extra=None: self._post_pack(
-                    wav, y_len, n_rows, words, passes, volume, tail, extra),
+                post=lambda wav, y_len, n_rows, words, extra: self._post_pack(
+                    wav, y_len, n_rows, words, out, extra),
                 ctls=ctls[lo:hi], got=durs)
             chunks.append(pcm)
             offsets += [offsets[-1] + int(o) for o in offs[1:]]
             n_model += [n * self.hop_size for n in y]
         pcm = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int16)
-        out = (pcm, np.asarray(offsets, dtype=np.int64), emos, n_model)
-        return out + (durs,) if return_durations else out
+        res = (pcm, np.asarray(offsets, dtype=np.int64), emos, n_model)
+        return res + (durs,) if return_durations else res
 
-    def _post_pack(self, wav, y_len, n_rows, words, passes, volume, tail, extra=None):
-        """The post passes over every row of the bucket, then the ragged
-        pack: one int16 buffer, in front of the samples the int32 words
-        [offsets (B + 1) | words (y_len, status, used_total: 2 B + 1) |
-        extra (int32, a controlled group's durations)]."""
-        B = wav.shape[0]
-        rows = self._post(wav, passes, volume, tail, lengths=y_len, length_scale=self.hop_size)
-        n_extra = 0 if extra is None else extra.numel()
-        header = self._header(B, n_extra)
-        out, _, _ = ops.pack_pcm(rows, y_len, self.hop_size, passes, tail, n_rows=n_rows,
-                                 header=header)
-        torch.cat(words, out=out[2 * (B + 1):2 * (3 * B + 2)].view(torch.int32))
-        if n_extra:
-            out[2 * (3 * B + 2):2 * (3 * B + 2 + n_extra)].view(torch.int32).copy_(
-                extra.reshape(-1))
-        return out
+    def _post_pack(self, wav, y_len, n_rows, words, out, extra=None):
+        """The post passes (_post under ``out``) over every row of the
+        bucket, then the ragged pack into the packed buffer (_pack)."""
+        rows = self._post(wav, out, lengths=y_len, length_scale=self.hop_size)
+        return self._pack(
+            wav.shape[0],
+            lambda header: ops.pack_pcm(rows, y_len, self.hop_size, out.passes, out.tail,
+                                        n_rows=n_rows, header=header)[0],
+            words, extra)
 
     # -- mixed requests: rows with their own speed, pitch, rate, volume, tail ------
     def infer_pcm_requests(self, requests, *, return_durations=False):
@@ -575,28 +655,21 @@ class EmoVITS(object):
             rows += [(t, s, e, r) for t, s, e in zip(texts, spkids, emos)]
         pcms, n_model, durs = [], [], []
         for lo, hi in self._groups(len(rows)):
-            group = rows[lo:hi]
-            ctl = [(self.sampling_rate if r.sampling_rate is None else int(r.sampling_rate), r)
-                   for _, _, _, r in group]
-            if hi - lo == 1 or not self._batchable([t for t, _, _, _ in group]):
-                for j, ((text, spkid, emo, r), (sr, _)) in enumerate(zip(group, ctl)):
-                    x_length, text_t, sid = self._one_tensors(spkid, text)
-                    got = [] if return_durations else None
-                    pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, r.duration_rate,
-                                                 r.pitch, sr, r.volume, r.tail_silence,
-                                                 row_ctl[lo + j], got)
-                    pcms.append(pcm)
-                    n_model.append(n)
-                    durs += got or []
+            texts, spkids, emos, reqs = (list(col) for col in zip(*rows[lo:hi]))
+            rates = [r.duration_rate for r in reqs]
+            outs = [self._output(r.pitch, r.sampling_rate, r.volume, r.tail_silence)
+                    for r in reqs]
+            if hi - lo == 1 or not self._batchable(texts):
+                got = self._one_by_one(spkids, texts, emos, rates, row_ctl[lo:hi], outs,
+                                       return_durations)
+                pcms += got[0]
+                n_model += got[1]
+                durs += got[2]
                 continue
-            passes = [self._post_passes(r.pitch, sr) for sr, r in ctl]
-            volumes = [r.volume for _, r in ctl]
-            tails = [int(r.tail_silence * sr) if r.tail_silence > 0 else 0 for sr, r in ctl]
             (pcm, offs), y = self._infer_graph_batch(
-                [t for t, _, _, _ in group], [e for _, _, e, _ in group],
-                [s for _, s, _, _ in group], None, rates=[r.duration_rate for _, r in ctl],
-                post=lambda wav, y_len, n_rows, words, extra=None: self._post_pack_rows(
-                    wav, y_len, n_rows, words, passes, volumes, tails, extra),
+                texts, emos, spkids, None, rates=rates,
+                post=lambda wav, y_len, n_rows, words, extra: self._post_pack_rows(
+                    wav, y_len, n_rows, words, outs, extra),
                 ctls=row_ctl[lo:hi], got=durs)
             pcms += [pcm[int(offs[i]):int(offs[i + 1])] for i in range(hi - lo)]
             n_model += [n * self.hop_size for n in y]
@@ -608,16 +681,18 @@ class EmoVITS(object):
                        + ((durs[lo:hi],) if return_durations else ()))
         return out
 
-    def _post_pack_rows(self, wav, y_len, n_rows, words, passes, volumes, tails, extra=None):
-        """_post_pack with per-row controls: ``passes`` / ``volumes`` /
-        ``tails`` of the group's rows (the padding rows of the bucket copy at
-        volume 1 with no tail).  max(1, most passes of a row) launches of
+    def _post_pack_rows(self, wav, y_len, n_rows, words, outs, extra=None):
+        """_post_pack with per-row controls: ``outs``, the _output of each of
+        the group's rows (the padding rows of the bucket copy at volume 1
+        with no tail).  max(1, most passes of a row) launches of
         ops.resample_rows: the last one writes the PCM, the ones before it
         fp32 and the lengths; a row's passes fill the first slots, (1, 1)
         the rest, which leaves its samples as they are."""
         B = wav.shape[0]
-        pad = B - len(passes)
-        passes, volumes, tails = passes + [[]] * pad, volumes + [1.0] * pad, tails + [0] * pad
+        pad = B - len(outs)
+        passes = [o.passes for o in outs] + [[]] * pad
+        volumes = [o.volume for o in outs] + [1.0] * pad
+        tails = [o.tail for o in outs] + [0] * pad
         n_launch = max(1, max(len(p) for p in passes))
         x, lengths, scale = wav, y_len, self.hop_size
         caps = [wav.shape[1]] * B
@@ -634,15 +709,10 @@ class EmoVITS(object):
         pcm = torch.empty(B, max(1, max(caps) + max(tails)), device=wav.device, dtype=torch.int16)
         ops.resample_rows(x, ratios, lengths=lengths, length_scale=scale, volumes=volumes,
                           pcm=True, out=pcm)
-        n_extra = 0 if extra is None else extra.numel()
-        header = self._header(B, n_extra)
-        out, _, _ = ops.pack_pcm_rows(pcm, y_len, self.hop_size, passes, tails, n_rows=n_rows,
-                                      header=header)
-        torch.cat(words, out=out[2 * (B + 1):2 * (3 * B + 2)].view(torch.int32))
-        if n_extra:
-            out[2 * (3 * B + 2):2 * (3 * B + 2 + n_extra)].view(torch.int32).copy_(
-                extra.reshape(-1))
-        return out
+        return self._pack(
+            B, lambda header: ops.pack_pcm_rows(pcm, y_len, self.hop_size, passes, tails,
+                                                n_rows=n_rows, header=header)[0],
+            words, extra)
 
     def _to_host(self, t):
         """One device-to-host copy of t through a reused pinned buffer, and
@@ -668,7 +738,7 @@ class EmoVITS(object):
         generator's final state are those of consecutive infer calls.
         Returns (wav [B, 1, frames * hop] on the device, y_len list), or with
         ``post(wav [B, frames * hop], y_len, n_rows, (y_len, status,
-        used_total))`` -> the int16 buffer of _post_pack: ((pcm, offsets),
+        used_total), extra)`` -> the packed buffer (_pack): ((pcm, offsets),
         y_len list) on the host after its single copy.  A row longer than the
         frame bucket re-runs the group at a larger bucket (same draws), an
         exhausted pool re-runs it with a pool twice as long.
@@ -678,20 +748,17 @@ class EmoVITS(object):
         under ("ctl", batch bucket, text bucket, frame bucket); rows without
         a control get the neutral one.  The frame bucket is at least what the
         rows whose total the host knows need.  The final durations [B, text
-        bucket] ride behind the header words of the packed buffer (``post`` is
-        then called with them as ``extra``), or with the words when there is
-        no post, and row i's int32 [t_x_i] is appended to ``got``."""
+        bucket] ride behind the header words of the packed buffer (``post``
+        gets them as ``extra``, None for a plain group), or with the words when
+        there is no post, and row i's int32 [t_x_i] is appended to ``got``."""
         n = len(texts)
         controlled = ctls is not None and any(c is not None for c in ctls)
         if controlled and rates is None:
             rates = [duration_rate] * n
         bb = self._batch_bucket(n)
         lengths = [t.shape[0] for t in texts]
-        xb = -(-max(lengths) // self.TX_BUCKET) * self.TX_BUCKET
-        x = np.zeros((n, max(lengths), texts[0].shape[1]), dtype=np.float32)
-        for i, t in enumerate(texts):
-            x[i, :lengths[i]] = t
-        x = torch.from_numpy(x).to(self.dtype).to(self.device)
+        xb = self._text_bucket(max(lengths))
+        x = self._text_rows(texts, lengths)
         emo = torch.cat(emos)
         sid = torch.tensor(spkids, dtype=torch.long)
         pool_mult = 1
@@ -703,33 +770,20 @@ class EmoVITS(object):
             control = dict(given=[c[0] for c in rows], tok_scale=[c[1] for c in rows],
                            target=[c[2] for c in rows])
             known = max([c[3] or 0 for c in rows])
+        n_extra = bb * xb if controlled else 0
         while True:
             tyb = self._ty_bucket.get(memo, 256)
             if known > tyb:
-                tyb = 1 << (known - 1).bit_length()
+                tyb = self._frame_bucket(known)
             key = (bb, xb, tyb, float(duration_rate)) if rates is None else ("rows", bb, xb, tyb)
             if controlled:
                 key = ("ctl", bb, xb, tyb)
-            run = self._graphs.pop(key, None)
-            if run is None:
-                while len(self._graphs) >= self.max_graphs:
-                    self._graphs.pop(next(iter(self._graphs)))
-                run = self.model.capture_infer_bucketed(
-                    xb, tyb, noise_len=self.noise.numel(), padded_text=True, batch=bb,
-                    length_scale=duration_rate if rates is None else torch.ones(bb),
-                    control=controlled)
-                run.static["noise"].copy_(self.noise.float())
-            self._graphs[key] = run  # most recently used last
+            run = self._cached_graph(key, lambda: self._capture_synthesis(
+                xb, tyb, batch=bb, control=controlled,
+                length_scale=duration_rate if rates is None else torch.ones(bb)))
             pool, state = ops.numpy_draw_pool(run.pool_len * pool_mult)
-            dur = None
             if pool_mult == 1:
-                if controlled:
-                    wav, y_len, status, used, dur, _ = run(x, emo, sid, lengths, pool, n,
-                                                           rates=rates, control=control)
-                elif rates is None:
-                    wav, y_len, status, used = run(x, emo, sid, lengths, pool, n)
-                else:
-                    wav, y_len, status, used = run(x, emo, sid, lengths, pool, n, rates=rates)
+                res = run(x, emo, sid, lengths, pool, n, rates=rates, control=control)
             else:
                 # the graph's pool is static: the (p < 2^-32 per row) longer
                 # pool runs the same kernels eagerly on the graph's inputs
@@ -740,43 +794,27 @@ class EmoVITS(object):
                     noise_start=torch.from_numpy(pool).to(self.device), n_rows=st["n_rows"],
                     control={k: st[k] for k in ("given", "tok_scale", "target")}
                     if controlled else None)
-                wav, y_len, status, used = res[:4]
-                dur = res[4] if controlled else None
-            words = (y_len, status, used)
-            n_extra = bb * xb if controlled else 0
+            wav, words, dur = res[0], res[1:4], res[4] if controlled else None
             if post is None:
                 host = torch.cat(words + ((dur.reshape(-1),) if controlled else ())).tolist()
+                y, st_rows, used, d = host[:n], host[bb:bb + n], host[2 * bb], host[2 * bb + 1:]
             else:
-                packed = (post(wav[:, 0], y_len, run.static["n_rows"], words, dur) if controlled
-                          else post(wav[:, 0], y_len, run.static["n_rows"], words))
-                header = self._header(bb, n_extra)
-                row_cap = (packed.numel() - header) // bb  # (the padding rows hold nothing)
-                buf = self._to_host(packed[:header + n * row_cap])
-                host = buf[2 * (bb + 1):2 * (3 * bb + 2 + n_extra)].view(np.int32).tolist()
-            y, st_rows, used = host[:n], host[bb:bb + n], host[2 * bb]
+                packed = post(wav[:, 0], words[0], run.static["n_rows"], words, dur)
+                pcm, offs, y, st_rows, used, d = self._unpack(packed, bb, n, n_extra)
             if max(y) > tyb:
-                np.random.set_state(state)  # re-run at a larger bucket: same draws
-                if tyb >= 4096:
-                    raise RuntimeError(f"utterance of {max(y)} frames exceeds the 4096-frame "
-                                       "noise buffer")
-                self._ty_bucket[memo] = min(4096, 1 << (max(y) - 1).bit_length())
+                self._grow_bucket(memo, state, tyb, max(y))  # same draws
                 continue
             if -2 in st_rows:
                 np.random.set_state(state)
                 pool_mult *= 2
                 continue
             if -1 in st_rows:
-                np.random.set_state(state)
-                raise ValueError(f"utterance of {y[st_rows.index(-1)]} frames does not fit the "
-                                 f"{self.noise.numel()}-sample noise buffer")
+                raise self._misfit(state, y[st_rows.index(-1)])
             ops.numpy_draw_commit(state, used)
             if controlled and got is not None:
-                d = np.asarray(host[2 * bb + 1:2 * bb + 1 + n_extra], np.int32).reshape(bb, xb)
+                d = np.asarray(d, np.int32).reshape(bb, xb)
                 got += [d[i, :lengths[i]].copy() for i in range(n)]
-            if post is None:
-                return wav, y
-            offs = buf[:2 * (bb + 1)].view(np.int32)[:n + 1]
-            return (buf[header:header + int(offs[n])], offs), y
+            return (wav, y) if post is None else ((pcm, offs), y)
 
     # -- voice conversion: waveform in, waveform out --------------------------------
     # frame buckets of the conversion graphs: powers of two, 256 .. 4096
@@ -801,7 +839,7 @@ class EmoVITS(object):
         if frames > cls.VC_MAX_FRAMES:
             raise ValueError(f"recording of {frames} frames exceeds the largest conversion bucket "
                              f"of {cls.VC_MAX_FRAMES} frames (chunk it)")
-        return max(cls.VC_MIN_FRAMES, 1 << max(0, int(frames) - 1).bit_length())
+        return cls._frame_bucket(frames)
 
     def _vc_plan(self, n_in, sampling_rate_in=None):
         """Host arithmetic of one recording of n_in samples at sampling_rate_in
@@ -841,25 +879,25 @@ class EmoVITS(object):
             x = x[:n]
         return x, frames, bucket
 
-    def _convert_rows(self, wavs, srcs, tgts, sampling_rate_in, noise_scale, post=None):
-        """1 .. MAX_BATCH recordings through one conversion graph, cached in
-        self._graphs under ("vc", batch bucket, frame bucket) (graph=False:
-        the same convert_bucketed call, eagerly).  Returns (wav_out [B, 1,
-        bucket * hop] fp32 on the device, frames list), or with ``post(wav
-        [B, bucket * hop], y_len int32 [B])`` its result in place of the
-        waveform.  No host sync: the host knows every length."""
+    def _vc_begin(self, what):
+        """The recording paths (``what``: convert, align) need a ROCm GPU and
+        the STFT parameters of the data config, which this returns."""
         if self.device.type != "cuda":
-            raise ops._lib.VitsAmdError("EmoVITS.convert: the vits_amd inference path runs on a "
+            raise ops._lib.VitsAmdError(f"EmoVITS.{what}: the vits_amd inference path runs on a "
                                         f"ROCm GPU only (got {self.device})")
-        stft = self._vc_stft()
-        hop = stft[1]
+        return self._vc_stft()
+
+    def _vc_upload(self, wavs, sampling_rate_in, noise_scale):
+        """1 .. MAX_BATCH recordings on the device (_vc_input each): (fp32
+        [n, longest] rows, zero past their ends; samples per row; frames per
+        row; the frame bucket of the longest; the batch bucket, 1 for one
+        row; the posterior noise [n, C, frame bucket] drawn from the device
+        generator this object owns and scaled, or None at noise_scale 0)."""
         rows = [self._vc_input(w, sampling_rate_in) for w in wavs]
         frames = [f for _, f, _ in rows]
         tyb = max(b for _, _, b in rows)
         n = len(rows)
         bb = 1 if n == 1 else self._batch_bucket(n)
-        src = [self._map_spkid(s) for s in srcs]
-        tgt = [self._map_spkid(s) for s in tgts]
         lens = [x.numel() for x, _, _ in rows]
         x = torch.zeros(n, max(lens), device=self.device)
         for i, (r, _, _) in enumerate(rows):
@@ -870,29 +908,43 @@ class EmoVITS(object):
                 self._vc_gen = torch.Generator(device=self.device)
             noise = torch.randn(n, self.inter_channels, tyb, device=self.device,
                                 generator=self._vc_gen) * float(noise_scale)
+        return x, lens, frames, tyb, bb, noise
+
+    def _pad_rows(self, v, bb, width=None, dtype=None):
+        """An input of the eager (graph=False) bucketed calls, zero-padded to
+        the batch bucket by hand: a tensor [n, w, ...] -> [bb, width or w,
+        ...]; with ``dtype`` a list of n ints -> a [bb] device tensor; None
+        stays None."""
+        if v is None:
+            return None
+        if dtype is not None:
+            return torch.tensor(list(v) + [0] * (bb - len(v)), dtype=dtype).to(self.device)
+        out = torch.zeros((bb, width or v.shape[1]) + tuple(v.shape[2:]), device=self.device,
+                          dtype=v.dtype)
+        out[:v.shape[0], :v.shape[1]] = v
+        return out
+
+    def _convert_rows(self, wavs, srcs, tgts, sampling_rate_in, noise_scale, post=None):
+        """1 .. MAX_BATCH recordings through one conversion graph, cached in
+        self._graphs under ("vc", batch bucket, frame bucket) (graph=False:
+        the same convert_bucketed call, eagerly).  Returns (wav_out [B, 1,
+        bucket * hop] fp32 on the device, frames list), or with ``post(wav
+        [B, bucket * hop], y_len int32 [B])`` its result in place of the
+        waveform.  No host sync: the host knows every length."""
+        stft = self._vc_begin("convert")
+        x, lens, frames, tyb, bb, noise = self._vc_upload(wavs, sampling_rate_in, noise_scale)
+        src = [self._map_spkid(s) for s in srcs]
+        tgt = [self._map_spkid(s) for s in tgts]
         if self.graph:
-            key = ("vc", bb, tyb)
-            run = self._graphs.pop(key, None)
-            if run is None:
-                while len(self._graphs) >= self.max_graphs:
-                    self._graphs.pop(next(iter(self._graphs)))
-                run = self.model.capture_convert_bucketed(tyb, batch=bb, stft=stft)
-            self._graphs[key] = run  # most recently used last
+            run = self._cached_graph(("vc", bb, tyb), lambda: self.model.capture_convert_bucketed(
+                tyb, batch=bb, stft=stft))
             out, y_len = run(x, lens, src, tgt, noise)
         else:
-            cap = tyb * hop + hop - 1
-            xs = torch.zeros(bb, cap, device=self.device)
-            xs[:n, :x.shape[1]] = x
-            pad = [0] * (bb - n)
-            dev = self.device
-            nz = None
-            if noise is not None:
-                nz = torch.zeros(bb, self.inter_channels, tyb, device=dev)
-                nz[:n] = noise
+            pad = self._pad_rows
             out, y_len = self.model.convert_bucketed(
-                xs, torch.tensor(lens + pad, dtype=torch.int32).to(dev),
-                torch.tensor(src + pad, dtype=torch.long).to(dev),
-                torch.tensor(tgt + pad, dtype=torch.long).to(dev), nz, tyb, stft=stft)
+                pad(x, bb, tyb * stft[1] + stft[1] - 1), pad(lens, bb, dtype=torch.int32),
+                pad(src, bb, dtype=torch.long), pad(tgt, bb, dtype=torch.long), pad(noise, bb),
+                tyb, stft=stft)
         if post is not None:
             return post(out[:, 0], y_len), frames
         return out, frames
@@ -917,17 +969,12 @@ class EmoVITS(object):
         sampling-rate resampling, volume, clip, int16, tail silence), the
         length read from the graph's y_len; one device-to-host copy, of the
         int16 PCM.  Returns (pcm int16 [n], n_model_samples)."""
-        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
-        tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
-        passes = self._post_passes(pitch, sampling_rate)
+        out = self._output(pitch, sampling_rate, volume, tail_silence)
         pcm, frames = self._convert_rows(
             [wav], [spkid_src], [spkid_tgt], sampling_rate_in, noise_scale,
-            post=lambda w, y_len: self._post(w, passes, volume, tail, lengths=y_len,
-                                             length_scale=self.hop_size))
-        n = n_out = frames[0] * self.hop_size
-        for up, down in passes:
-            n_out = ops.resample_out_len(n_out, up, down)
-        return pcm[0, :n_out + tail].cpu().numpy(), n
+            post=lambda w, y_len: self._post(w, out, lengths=y_len, length_scale=self.hop_size))
+        n = frames[0] * self.hop_size
+        return pcm[0, :self._n_out(n, out.passes) + out.tail].cpu().numpy(), n
 
     def convert_pcm_batch(self, items, *, sampling_rate_in=None, noise_scale=0.0, pitch=1.0,
                           sampling_rate=None, volume=1.0, tail_silence=0.0):
@@ -940,15 +987,13 @@ class EmoVITS(object):
         the post passes over its rows, the ragged pack and ONE device-to-host
         copy."""
         items = list(items)
-        sampling_rate = self.sampling_rate if sampling_rate is None else int(sampling_rate)
-        tail = int(tail_silence * sampling_rate) if tail_silence > 0 else 0
-        passes = self._post_passes(pitch, sampling_rate)
+        out = self._output(pitch, sampling_rate, volume, tail_silence)
         chunks, offsets, n_model = [], [0], []
         for lo, hi in self._groups(len(items)):
             if hi - lo == 1:
                 pcm, n = self.convert_pcm(*items[lo], sampling_rate_in=sampling_rate_in,
                                           noise_scale=noise_scale, pitch=pitch,
-                                          sampling_rate=sampling_rate, volume=volume,
+                                          sampling_rate=out.sampling_rate, volume=volume,
                                           tail_silence=tail_silence)
                 chunks.append(pcm)
                 offsets.append(offsets[-1] + len(pcm))
@@ -959,17 +1004,13 @@ class EmoVITS(object):
 
             def post(w, y_len):
                 zeros = torch.zeros(bb + 1, device=w.device, dtype=torch.int32)
-                return self._post_pack(w, y_len, n, (y_len, zeros[:bb], zeros[bb:]), passes,
-                                       volume, tail)
+                return self._post_pack(w, y_len, n, (y_len, zeros[:bb], zeros[bb:]), out)
 
             packed, frames = self._convert_rows(
                 [w for w, _, _ in items[lo:hi]], [s for _, s, _ in items[lo:hi]],
                 [t for _, _, t in items[lo:hi]], sampling_rate_in, noise_scale, post=post)
-            header = -(-2 * (3 * bb + 2) // 8) * 8
-            row_cap = (packed.numel() - header) // bb  # (the padding rows hold nothing)
-            buf = self._to_host(packed[:header + n * row_cap])
-            offs = buf[:2 * (bb + 1)].view(np.int32)[:n + 1]
-            chunks.append(buf[header:header + int(offs[n])])
+            pcm, offs = self._unpack(packed, bb, n)[:2]
+            chunks.append(pcm)
             offsets += [offsets[-1] + int(o) for o in offs[1:]]
             n_model += [f * self.hop_size for f in frames]
         pcm = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int16)
@@ -987,11 +1028,7 @@ class EmoVITS(object):
         after ONE device-to-host copy.  The host knows every length: a
         recording with fewer frames than tokens is refused here.  ``device``:
         [(durations int32 [Tx] on the device, frames)] with no copy at all."""
-        if self.device.type != "cuda":
-            raise ops._lib.VitsAmdError("EmoVITS.align: the vits_amd inference path runs on a "
-                                        f"ROCm GPU only (got {self.device})")
-        stft = self._vc_stft()
-        hop = stft[1]
+        stft = self._vc_begin("align")
         n = len(wavs)
         tokens = [int(np.shape(t)[0]) for t in texts]
         for w, t in zip(wavs, tokens):
@@ -999,57 +1036,26 @@ class EmoVITS(object):
             if t < 1 or frames < t:
                 raise ValueError(f"recording of {frames} frames cannot be aligned with {t} "
                                  "tokens: every token takes at least one frame")
-        xb = -(-max(tokens) // self.TX_BUCKET) * self.TX_BUCKET
+        xb = self._text_bucket(max(tokens))
         if xb > self.ALIGN_MAX_TOKENS:
             raise ValueError(f"text of {max(tokens)} tokens exceeds the alignment kernel's "
                              f"{self.ALIGN_MAX_TOKENS}")
-        rows = [self._vc_input(w, sampling_rate_in) for w in wavs]
-        frames = [f for _, f, _ in rows]
-        tyb = max(b for _, _, b in rows)
-        bb = 1 if n == 1 else self._batch_bucket(n)
+        wav, lens, frames, tyb, bb, noise = self._vc_upload(wavs, sampling_rate_in, noise_scale)
         resolved = [self._resolve(s, e) for s, e in zip(spkids, emos)]
         sids = [int(s) for s, _ in resolved]
         emo = torch.cat([e for _, e in resolved])
-        lens = [r.numel() for r, _, _ in rows]
-        wav = torch.zeros(n, max(lens), device=self.device)
-        for i, (r, _, _) in enumerate(rows):
-            wav[i, :lens[i]] = r
-        x = np.zeros((n, max(tokens), np.shape(texts[0])[1]), dtype=np.float32)
-        for i, t in enumerate(texts):
-            x[i, :tokens[i]] = t
-        x = torch.from_numpy(x).to(self.dtype).to(self.device)
-        noise = None
-        if noise_scale > 0:
-            if self._vc_gen is None:
-                self._vc_gen = torch.Generator(device=self.device)
-            noise = torch.randn(n, self.inter_channels, tyb, device=self.device,
-                                generator=self._vc_gen) * float(noise_scale)
+        x = self._text_rows(texts, tokens)
         if self.graph:
-            key = ("align", bb, xb, tyb)
-            run = self._graphs.pop(key, None)
-            if run is None:
-                while len(self._graphs) >= self.max_graphs:
-                    self._graphs.pop(next(iter(self._graphs)))
-                run = self.model.capture_align_bucketed(xb, tyb, batch=bb, stft=stft)
-            self._graphs[key] = run  # most recently used last
+            run = self._cached_graph(
+                ("align", bb, xb, tyb),
+                lambda: self.model.capture_align_bucketed(xb, tyb, batch=bb, stft=stft))
             dur, scores, _ = run(wav, lens, x, tokens, emo, sids, noise)
         else:
-            dev = self.device
-            ws = torch.zeros(bb, tyb * hop + hop - 1, device=dev)
-            ws[:n, :wav.shape[1]] = wav
-            xs = torch.zeros(bb, xb, x.shape[2], device=dev, dtype=x.dtype)
-            xs[:n, :x.shape[1]] = x
-            es = torch.zeros(bb, emo.shape[1], device=dev, dtype=emo.dtype)
-            es[:n] = emo
-            pad = [0] * (bb - n)
-            nz = None
-            if noise is not None:
-                nz = torch.zeros(bb, self.inter_channels, tyb, device=dev)
-                nz[:n] = noise
+            pad = self._pad_rows
             dur, scores, _ = self.model.align_bucketed(
-                ws, torch.tensor(lens + pad, dtype=torch.int32).to(dev), xs,
-                torch.tensor(tokens + pad, dtype=torch.int32).to(dev), es,
-                torch.tensor(sids + pad, dtype=torch.long).to(dev), nz, xb, tyb, stft=stft)
+                pad(wav, bb, tyb * stft[1] + stft[1] - 1), pad(lens, bb, dtype=torch.int32),
+                pad(x, bb, xb), pad(tokens, bb, dtype=torch.int32), pad(emo, bb),
+                pad(sids, bb, dtype=torch.long), pad(noise, bb), xb, tyb, stft=stft)
         if device:  # (infer_pcm_like: the durations stay on the device, nothing is copied)
             return [(dur[i, :tokens[i]], frames[i]) for i in range(n)]
         host = self._to_host(torch.cat([dur[:n], scores[:n].view(torch.int32)], 1)).reshape(n, -1)
@@ -1091,6 +1097,44 @@ class EmoVITS(object):
     # frame buckets are powers of two from 256 up to the noise buffer's 4096
     TX_BUCKET = 32
 
+    @classmethod
+    def _text_bucket(cls, t):
+        """The smallest multiple of TX_BUCKET that holds t tokens."""
+        return -(-t // cls.TX_BUCKET) * cls.TX_BUCKET
+
+    @classmethod
+    def _frame_bucket(cls, n, cap=None):
+        """The smallest frame bucket that holds n frames: a power of two, at
+        least 256; with ``cap`` at most that (the 4096 frames of the noise
+        buffer, where a bucket grows towards it)."""
+        b = max(cls.VC_MIN_FRAMES, 1 << max(0, int(n) - 1).bit_length())
+        return b if cap is None else min(cap, b)
+
+    def _text_rows(self, texts, lengths):
+        """Texts of ``lengths`` tokens as one [n, longest, c] tensor on the
+        device in the model's dtype, zero past each row's end."""
+        x = np.zeros((len(texts), max(lengths), np.shape(texts[0])[1]), dtype=np.float32)
+        for i, t in enumerate(texts):
+            x[i, :lengths[i]] = t
+        return torch.from_numpy(x).to(self.dtype).to(self.device)
+
+    def _grow_bucket(self, memo, state, tyb, n):
+        """An utterance of n frames did not fit its frame bucket ``tyb``:
+        restore numpy's generator (the re-run makes the same draws) and keep
+        a bucket that holds n under ``memo``, or raise RuntimeError when the
+        bucket already is the noise buffer's 4096 frames."""
+        np.random.set_state(state)
+        if tyb >= 4096:
+            raise RuntimeError(f"utterance of {n} frames exceeds the 4096-frame noise buffer")
+        self._ty_bucket[memo] = self._frame_bucket(n, cap=4096)
+
+    def _misfit(self, state, n):
+        """The ValueError of an utterance of n frames that is longer than the
+        noise buffer, with numpy's generator put back."""
+        np.random.set_state(state)
+        return ValueError(f"utterance of {n} frames does not fit the "
+                          f"{self.noise.numel()}-sample noise buffer")
+
     def _infer_graph(self, text_t, emo, sid, duration_rate, post=None, ctl=None, got=None):
         """One replay of the whole-utterance graph; the one host sync is the
         waveform copy (y_len read with it).  A bucket that turns out too
@@ -1109,22 +1153,15 @@ class EmoVITS(object):
         bucket and grown by the re-run below.  ``got`` (a list): the final
         durations (int32 [t_x]) are appended to it."""
         t_x = text_t.shape[1]
-        xb = -(-t_x // self.TX_BUCKET) * self.TX_BUCKET
+        xb = self._text_bucket(t_x)
         memo = (xb, duration_rate) if ctl is None else ("ctl", xb)
         while True:
             tyb = self._ty_bucket.get(memo, 256)
             if ctl is not None and ctl[3] is not None:
-                tyb = max(256, 1 << (max(ctl[3], 1) - 1).bit_length())
+                tyb = self._frame_bucket(ctl[3])
             key = (xb, tyb, float(duration_rate)) if ctl is None else ("ctl", 1, xb, tyb)
-            run = self._graphs.pop(key, None)
-            if run is None:
-                while len(self._graphs) >= self.max_graphs:
-                    self._graphs.pop(next(iter(self._graphs)))
-                run = self.model.capture_infer_bucketed(
-                    xb, tyb, noise_len=self.noise.numel(), padded_text=True,
-                    length_scale=duration_rate, control=ctl is not None)
-                run.static["noise"].copy_(self.noise.float())
-            self._graphs[key] = run  # most recently used last
+            run = self._cached_graph(key, lambda: self._capture_synthesis(
+                xb, tyb, length_scale=duration_rate, control=ctl is not None))
             # infer.py:173's np.random.randint(len - nl), drawn on the device
             # from raw words of numpy's own generator: the same start as the
             # reference, and the generator ends where the reference's does
@@ -1152,17 +1189,12 @@ class EmoVITS(object):
                 continue
             if n <= tyb:
                 if used < 0:
-                    np.random.set_state(state)
-                    raise ValueError(f"utterance of {n} frames does not fit the "
-                                     f"{self.noise.numel()}-sample noise buffer")
+                    raise self._misfit(state, n)
                 ops.numpy_draw_commit(state, used)
                 if post is not None:
                     return posted, n
                 return wav[0, 0, :n * self.hop_size].float().cpu().numpy()
-            np.random.set_state(state)  # re-run at a larger bucket: same draw
-            if tyb >= 4096:
-                raise RuntimeError(f"utterance of {n} frames exceeds the 4096-frame noise buffer")
-            self._ty_bucket[memo] = min(4096, 1 << (n - 1).bit_length())
+            self._grow_bucket(memo, state, tyb, n)  # re-run at a larger bucket: same draw
 
 
 def main(argv=None):

@@ -363,6 +363,13 @@ def _control_fill(static, rows, batch, t_x):
         static["given"][i, :g.numel()].copy_(g.reshape(-1).to(torch.int32))
 
 
+def _fill_rows(buf, src, n, w=None):
+    """One replay input: zero the static buffer, then copy ``src`` (n rows)
+    into its first n rows (``w``: into their first w columns)."""
+    buf.zero_()
+    (buf[:n] if w is None else buf[:n, :w]).copy_(src)
+
+
 class SynthesizerTrn(nn.Module):
     """Synthesizer for training and inference (models.py:411-575)."""
 
@@ -669,6 +676,34 @@ class SynthesizerTrn(nn.Module):
             return (o.to(m_p.dtype), lens[0::len(lens) - 1]) + plan
         return (o.to(m_p.dtype), lens[0]) + plan
 
+    # ------------------------------------------------------------ hipGraphs
+    # Every capture_* below is the same three steps: static input buffers, a
+    # ``body`` over them captured by _capture_body, and a ``run`` closure that
+    # fills the buffers, replays and returns the captured outputs.
+    @staticmethod
+    def _capture_body(body, warmup, dev):
+        """Warm ``body`` up on a side stream, then capture it on the current
+        one (torch.cuda.CUDAGraph is HIP graphs on ROCm): (graph, its outputs)."""
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                body()
+        torch.cuda.current_stream(dev).wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = body()
+        return graph, out
+
+    @staticmethod
+    def _graph_run(run, graph, static, **attrs):
+        """``run`` with its graph, its static buffers and ``attrs`` (t_x, t_y,
+        batch, pool_len, output: what the capture has) attached."""
+        run.graph, run.static = graph, static
+        for k, v in attrs.items():
+            setattr(run, k, v)
+        return run
+
     @torch.no_grad()
     def capture_infer_bucketed(self, t_x, t_y, *, noise_len=None, padded_text=False,
                                length_scale=1.0, warmup=2, batch=1, pool_len=None,
@@ -733,15 +768,7 @@ class SynthesizerTrn(nn.Module):
                                        noise_start=static["start"] if noise_len else None,
                                        control=ctl)
 
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                body()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = body()
+        graph, out = self._capture_body(body, warmup, dev)
 
         def run(x, emo, sid, noise=None, noise_start=None, x_length=None, rate=None,
                 control=None):
@@ -769,10 +796,7 @@ class SynthesizerTrn(nn.Module):
             graph.replay()
             return out
 
-        run.graph = graph
-        run.static = static
-        run.t_y = t_y
-        return run
+        return self._graph_run(run, graph, static, t_y=t_y)
 
     def _capture_infer_batch(self, t_x, t_y, batch, noise_len, padded_text, length_scale, warmup,
                              pool_len, control=False):
@@ -802,15 +826,7 @@ class SynthesizerTrn(nn.Module):
                                        noise_start=static["pool"], n_rows=static["n_rows"],
                                        control=ctl)
 
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                body()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = body()
+        graph, out = self._capture_body(body, warmup, dev)
 
         def run(x, emo, sid, x_lengths, pool, n_rows=None, rates=None, control=None):
             n = x.shape[0] if n_rows is None else int(n_rows)
@@ -838,13 +854,10 @@ class SynthesizerTrn(nn.Module):
                 raise ValueError(f"batched replay: {n} rows of lengths {lengths} in x "
                                  f"{tuple(x.shape)} do not fit [{batch}, {t_x}]")
             static["xl"].copy_(torch.tensor(lengths + [0] * (batch - n), dtype=torch.int32))
-            static["x"].zero_()
-            static["x"][:n, :x.shape[1]].copy_(x[:n])
+            _fill_rows(static["x"], x[:n], n, x.shape[1])
             static["x"].masked_fill_(cols >= static["xl"].view(batch, 1, 1), 0)
-            static["emo"].zero_()
-            static["emo"][:n].copy_(emo[:n])
-            static["sid"].zero_()
-            static["sid"][:n].copy_(torch.as_tensor(sid)[:n])
+            _fill_rows(static["emo"], emo[:n], n)
+            _fill_rows(static["sid"], torch.as_tensor(sid)[:n], n)
             pool = torch.as_tensor(pool, dtype=torch.int32).view(-1)
             if pool.numel() != P:
                 raise ValueError(f"batched replay: the pool must have {P} words, got {pool.numel()}")
@@ -853,12 +866,7 @@ class SynthesizerTrn(nn.Module):
             graph.replay()
             return out
 
-        run.graph = graph
-        run.static = static
-        run.t_y = t_y
-        run.batch = batch
-        run.pool_len = P
-        return run
+        return self._graph_run(run, graph, static, t_y=t_y, batch=batch, pool_len=P)
 
     # ----------------------------------- the audio side of VC and alignment
     def _audio_latents(self, spec, noise, lens, g, keep=False):
@@ -991,12 +999,9 @@ class SynthesizerTrn(nn.Module):
                 raise ValueError(f"convert replay: wav {tuple(wav.shape)} does not fit "
                                  f"[{batch}, {cap}]")
             static["wav"][:n, :wav.shape[1]].copy_(wav)
-            static["n"].zero_()
-            static["n"][:n].copy_(_ints(n_samples, n, torch.int32))
-            static["src"].zero_()
-            static["src"][:n].copy_(_ints(sid_src, n, torch.long))
-            static["tgt"].zero_()
-            static["tgt"][:n].copy_(_ints(sid_tgt, n, torch.long))
+            _fill_rows(static["n"], _ints(n_samples, n, torch.int32), n)
+            _fill_rows(static["src"], _ints(sid_src, n, torch.long), n)
+            _fill_rows(static["tgt"], _ints(sid_tgt, n, torch.long), n)
             if noise is None:
                 static["noise"].zero_()
             else:
@@ -1004,25 +1009,7 @@ class SynthesizerTrn(nn.Module):
             graph.replay()
             return out
 
-        run.graph = graph
-        run.static = static
-        run.t_y = t_y
-        run.batch = batch
-        return run
-
-    @staticmethod
-    def _capture_body(body, warmup, dev):
-        """Warm ``body`` up on a side stream, then capture it: (graph, its outputs)."""
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                body()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = body()
-        return graph, out
+        return self._graph_run(run, graph, static, t_y=t_y, batch=batch)
 
     @staticmethod
     def _row_ints(v, n, dtype):
@@ -1134,16 +1121,11 @@ class SynthesizerTrn(nn.Module):
             if x.shape[0] != n or x.shape[1] > t_x:
                 raise ValueError(f"align replay: x {tuple(x.shape)} does not fit [{n}, {t_x}, c]")
             static["wav"][:n, :wav.shape[1]].copy_(wav)
-            static["n"].zero_()
-            static["n"][:n].copy_(_ints(n_samples, n, torch.int32))
-            static["x"].zero_()
-            static["x"][:n, :x.shape[1]].copy_(x)
-            static["xl"].zero_()
-            static["xl"][:n].copy_(_ints(x_lengths, n, torch.int32))
-            static["emo"].zero_()
-            static["emo"][:n].copy_(emo)
-            static["sid"].zero_()
-            static["sid"][:n].copy_(_ints(sid, n, torch.long))
+            _fill_rows(static["n"], _ints(n_samples, n, torch.int32), n)
+            _fill_rows(static["x"], x, n, x.shape[1])
+            _fill_rows(static["xl"], _ints(x_lengths, n, torch.int32), n)
+            _fill_rows(static["emo"], emo, n)
+            _fill_rows(static["sid"], _ints(sid, n, torch.long), n)
             if noise is None:
                 static["noise"].zero_()
             else:
@@ -1151,14 +1133,9 @@ class SynthesizerTrn(nn.Module):
             graph.replay()
             return out
 
-        run.graph = graph
-        run.static = static
-        run.t_x = t_x
-        run.t_y = t_y
-        run.batch = batch
-        return run
+        return self._graph_run(run, graph, static, t_x=t_x, t_y=t_y, batch=batch)
 
-    # ------------------------------------------------------------ hipGraphs
+    # --------------------------------------- the two halves, captured apart
     @torch.no_grad()
     def capture_infer_p1(self, t_x, warmup=2):
         """Capture infer_p1 for one utterance of t_x tokens into a hipGraph
@@ -1174,15 +1151,7 @@ class SynthesizerTrn(nn.Module):
         def body():
             return self.infer_p1(static["x"], static["emo"], static["sid"])
 
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                body()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = body()
+        graph, out = self._capture_body(body, warmup, dev)
 
         def run(x, emo, sid):
             static["x"].copy_(x)
@@ -1191,9 +1160,7 @@ class SynthesizerTrn(nn.Module):
             graph.replay()
             return out
 
-        run.graph = graph
-        run.static = static
-        return run
+        return self._graph_run(run, graph, static)
 
     @torch.no_grad()
     def capture_infer_p2(self, batch, t_x, t_y, warmup=2):
@@ -1215,15 +1182,7 @@ class SynthesizerTrn(nn.Module):
             fplan.run_(z, static["g"])
             return gplan.run(z, static["g"])
 
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                body()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = body()
+        graph, out = self._capture_body(body, warmup, dev)
 
         def run(attn, m_p, s_p, g, noise):
             static["attn"].copy_(attn)
@@ -1234,10 +1193,7 @@ class SynthesizerTrn(nn.Module):
             graph.replay()
             return out
 
-        run.graph = graph
-        run.static = static
-        run.output = out
-        return run
+        return self._graph_run(run, graph, static, output=out)
 
 
 # train.py's discriminator lives beside the generator in the reference's
