@@ -1073,6 +1073,30 @@ int vits_pack_pcm_rows(const int16_t* rows, int64_t bstride, int cap, const int3
                        const int32_t* n_rows, int batch, int32_t* offsets, int16_t* out,
                        int64_t out_cap, void* stream);
 
+/* ---------------------------------------------------------------------- */
+/* Window copy of long-recording voice conversion: n_jobs <= 64 ranges of   */
+/* fp32 elements in ONE launch.  For job j and channel r < channels:        */
+/*   dst[dst_off + r * dst_rstride + i] = src[src_off + r * src_rstride + i]*/
+/*                                                          for i < len,    */
+/*   dst[dst_off + r * dst_rstride + i] = 0       for len <= i < fill_len,  */
+/* and nothing else is written.  Offsets, lengths and strides count         */
+/* elements; src_numel / dst_numel are the sizes of the two buffers, and a  */
+/* job that reads or writes outside them is refused.  jobs is a HOST array, */
+/* copied into the kernel arguments: the call keeps no pointer to it and    */
+/* can be captured.  Accesses are 16 bytes wide where the source and the    */
+/* destination of a (job, channel) are co-aligned, single elements          */
+/* otherwise.  VITS_E_ARG: a null pointer, a pointer off a 4-byte boundary, */
+/* n_jobs < 1, channels < 1, a negative offset, stride, size or length,     */
+/* fill_len < len.  VITS_E_SHAPE: n_jobs > 64, channels > 65535, a job      */
+/* outside its buffers, channels > 1 with dst_rstride < fill_len.           */
+/* ---------------------------------------------------------------------- */
+typedef struct {
+  int64_t src_off, dst_off, len, fill_len;
+} vits_window_job;
+int vits_copy_windows(const float* src, int64_t src_numel, int64_t src_rstride, float* dst,
+                      int64_t dst_numel, int64_t dst_rstride, const vits_window_job* jobs,
+                      int n_jobs, int channels, void* stream);
+
 /* library introspection */
 const char* vits_amd_version(void);
 int vits_amd_device_arch(char* buf, int len);

@@ -314,6 +314,16 @@ class PostRow(C.Structure):
     ]
 
 
+class WindowJob(C.Structure):
+    """include/vits_amd.h vits_window_job (one range of vits_copy_windows)."""
+    _fields_ = [
+        ("src_off", C.c_int64),
+        ("dst_off", C.c_int64),
+        ("len", C.c_int64),
+        ("fill_len", C.c_int64),
+    ]
+
+
 _SIGS = {
     "vits_conv1d_forward": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_void_p]),
     "vits_conv1d_forward_seq": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_void_p]),
@@ -561,6 +571,11 @@ _SIGS = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_float, C.c_void_p,
          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    ),
+    "vits_copy_windows": (
+        C.c_int,
+        [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(WindowJob),
+         C.c_int, C.c_int, C.c_void_p],
     ),
     "vits_amd_version": (C.c_char_p, []),
     "vits_amd_device_arch": (C.c_int, [C.c_char_p, C.c_int]),

@@ -50,6 +50,17 @@ class _Output(NamedTuple):
     passes: list  # (up, down) resampling passes (EmoVITS._post_passes)
 
 
+class _Window(NamedTuple):
+    """One window of a long recording (EmoVITS._long_plan)."""
+    core_lo: int  # it owns the frames [core_lo, core_hi) of the recording
+    core_hi: int
+    a: int  # its row spans the frames [a, b)
+    b: int
+    s0: int  # and the samples [s0, s1)
+    s1: int
+    core_off: int  # samples into the row at which the core starts
+
+
 class EmoVITS(object):
     def __init__(self, checkpoint_path=None, device=None, *, loglv=0, hps=None, model=None,
                  graph_cache=0, graph=True, max_graphs=16, half=True):
@@ -847,6 +858,11 @@ class EmoVITS(object):
         samples at the model rate, frames, frame bucket).  Raises ValueError
         for a recording of at most pad = (n_fft - hop) / 2 samples (the
         reflect padding needs more) or of more than 4096 frames."""
+        ratio, n, frames = self._vc_lengths(n_in, sampling_rate_in)
+        return ratio, n, frames, self._vc_bucket(frames)
+
+    def _vc_lengths(self, n_in, sampling_rate_in=None):
+        """_vc_plan without the bucket, so without the cap of 4096 frames."""
         n_fft, hop, _ = self._vc_stft()
         ratio, n = None, int(n_in)
         if sampling_rate_in is not None and int(sampling_rate_in) != self.sampling_rate:
@@ -856,16 +872,17 @@ class EmoVITS(object):
         if n <= pad:
             raise ValueError(f"recording of {n} samples at {self.sampling_rate} Hz is too short: "
                              f"voice conversion needs more than {pad}")
-        frames = n // hop
-        return ratio, n, frames, self._vc_bucket(frames)
+        return ratio, n, n // hop
 
-    def _vc_input(self, wav, sampling_rate_in):
+    def _vc_input(self, wav, sampling_rate_in, capped=True):
         """One recording on the device at the model rate: (fp32 [n], frames,
         bucket).  int16 is scaled by 1 / 32768 (data_utils), floats are taken
         as they are; another rate takes one ops.resample_poly pass (the host
-        knows every length: no sync)."""
+        knows every length: no sync).  ``capped=False`` (convert_long): any
+        number of frames, and None for the bucket."""
         wav = np.asarray(wav).reshape(-1)
-        ratio, n, frames, bucket = self._vc_plan(wav.shape[0], sampling_rate_in)
+        ratio, n, frames = self._vc_lengths(wav.shape[0], sampling_rate_in)
+        bucket = self._vc_bucket(frames) if capped else None
         if wav.dtype == np.int16:
             x = torch.from_numpy(wav.astype(np.float32) / 32768.0)
         elif np.issubdtype(wav.dtype, np.floating):
@@ -1015,6 +1032,183 @@ class EmoVITS(object):
             n_model += [f * self.hop_size for f in frames]
         pcm = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int16)
         return pcm, np.asarray(offsets, dtype=np.int64), n_model
+
+    # -- long recordings: overlapping windows, seamless cores --------
+    # the frame bucket of a window (measured: profiles/vc_long_latency.txt)
+    LONG_WINDOW_FRAMES = 4096
+    # the resampler and the output stage carry every length as a C int
+    LONG_MAX_SAMPLES = 2 ** 31 - 1
+
+    def _long_plan(self, n, window_frames, context):
+        """The windows of a recording of n samples at the model rate, F = n //
+        hop frames, for rows of ``window_frames`` frames with ``context``
+        frames between an artificial edge and the core: Cf = window_frames -
+        2 * context core frames per window (ValueError when Cf < 1).  Window
+        w owns the core frames [w * Cf, min((w + 1) * Cf, F)) and its row
+        spans the frames [a, b) = [max(0, w * Cf - context), min(F, (w + 1) *
+        Cf + context)), the samples [a * hop, b * hop); a row that reaches
+        the last frame (b == F: the last window, and every earlier one whose
+        right context does) runs to sample n, so the remainder and the
+        reflection at the true end are the whole recording's, as those at
+        the true start are the rows' with a == 0.  (A row with b == F cut at
+        F * hop would fold its reflection n % hop samples early: an
+        artificial edge with no context behind it.)  W = ceil(F / Cf)
+        windows, none empty.  Host arithmetic only."""
+        hop = self.hop_size
+        n, wf, ctx = int(n), int(window_frames), int(context)
+        cf = wf - 2 * ctx
+        if ctx < 0 or cf < 1:
+            raise ValueError(f"windows of {wf} frames leave no core beside 2 x {ctx} frames of "
+                             "context")
+        F = n // hop
+        plan = []
+        for w in range(-(-F // cf)):
+            lo, hi = w * cf, min((w + 1) * cf, F)
+            a, b = max(0, lo - ctx), min(F, (w + 1) * cf + ctx)
+            plan.append(_Window(lo, hi, a, b, a * hop, n if b == F else b * hop, (lo - a) * hop))
+        return plan
+
+    def _long_check(self, n_in, sampling_rate_in, out=None):
+        """The host arithmetic of a long recording, before anything is
+        uploaded: its frames at the model rate.  ValueError for what
+        _vc_lengths refuses, and for a recording whose samples, at the input
+        rate, at the model rate or after any pass of the output stage
+        ``out`` (tail included), exceed LONG_MAX_SAMPLES."""
+        n_in = int(n_in)
+        worst, frames = n_in, 0
+        if n_in <= self.LONG_MAX_SAMPLES:
+            _, n, frames = self._vc_lengths(n_in, sampling_rate_in)
+            worst = max(worst, n)
+            if out is not None:
+                m = frames * self.hop_size
+                for up, down in out.passes:
+                    m = ops.resample_out_len(m, up, down)
+                    worst = max(worst, m)
+                worst = max(worst, m + out.tail)
+        if worst > self.LONG_MAX_SAMPLES:
+            raise ValueError(f"recording of {n_in} samples comes to {worst} at some stage: the "
+                             f"resampler and the output stage take at most "
+                             f"{self.LONG_MAX_SAMPLES} per row")
+        return frames
+
+    def _convert_windows(self, wav, spkid_src, spkid_tgt, sampling_rate_in, noise_scale,
+                         window_frames, context):
+        """A recording of any length, uploaded once (_vc_input without the
+        cap), through the windows of _long_plan (_run_windows): (the stitched
+        waveform fp32 [1, max(1, F * hop)] on the device, F).  A recording of
+        at most window_frames frames is ONE window, the whole of it, with no
+        artificial edge.  noise_scale > 0: ONE [C, F] posterior draw for the
+        whole recording from the generator this object owns."""
+        stft = self._vc_begin("convert_long")
+        wf = self.LONG_WINDOW_FRAMES if window_frames is None else int(window_frames)
+        if not self.VC_MIN_FRAMES <= wf <= self.VC_MAX_FRAMES or self._frame_bucket(wf) != wf:
+            raise ValueError(f"window_frames must be a conversion bucket (a power of two, "
+                             f"{self.VC_MIN_FRAMES} .. {self.VC_MAX_FRAMES}), got {wf}")
+        x, F, _ = self._vc_input(wav, sampling_rate_in, capped=False)
+        if 0 < F <= wf:
+            plan = [_Window(0, F, 0, F, 0, x.numel(), 0)]
+        else:
+            ctx = self.model.vc_context_frames(stft) if context is None else int(context)
+            plan = self._long_plan(x.numel(), wf, ctx)
+        noise = None
+        if noise_scale > 0:
+            if self._vc_gen is None:
+                self._vc_gen = torch.Generator(device=self.device)
+            noise = torch.randn(self.inter_channels, max(1, F), device=self.device,
+                                generator=self._vc_gen) * float(noise_scale)
+        out = self._run_windows(x, plan, wf, self._map_spkid(spkid_src),
+                                self._map_spkid(spkid_tgt), noise)
+        return out, F
+
+    def _run_windows(self, x, plan, wf, src, tgt, noise=None):
+        """The windows ``plan`` of the recording x (fp32 [n] on the device) as
+        rows of ``wf`` frames, stitched: fp32 [1, max(1, F * hop)].  Per group
+        of up to MAX_BATCH windows one ops.copy_windows gathers the rows into
+        the static wav of the conversion graph cached under ("vc", batch
+        bucket, wf), zero past each row's length; one more gathers the rows'
+        slices of ``noise`` (fp32 [C, F], scaled; None: the posterior mean)
+        into its static noise, so overlapping rows see the same noise; the
+        graph replays; a third launch scatters the cores into their places.
+        graph=False: the same gathers into fresh tensors and convert_bucketed
+        eagerly.  No host sync: the host knows every length."""
+        stft = self._vc_stft()
+        hop = stft[1]
+        F = x.numel() // hop
+        C, cap = self.inter_channels, wf * hop + hop - 1
+        out = torch.empty(1, max(1, F * hop), device=self.device)
+        for lo, hi in self._groups(len(plan)):
+            rows = plan[lo:hi]
+            m = len(rows)
+            bb = 1 if m == 1 else self._batch_bucket(m)
+            lens = [w.s1 - w.s0 for w in rows]
+            if self.graph:
+                run = self._cached_graph(("vc", bb, wf), lambda: self.model.capture_convert_bucketed(
+                    wf, batch=bb, stft=stft))
+                wav_rows, noise_rows = run.static["wav"], run.static["noise"]
+                if noise is None:
+                    noise_rows.zero_()
+            else:
+                wav_rows = torch.zeros(bb, cap, device=self.device)
+                noise_rows = None if noise is None else torch.zeros(bb, C, wf, device=self.device)
+            ops.copy_windows(x, wav_rows, [(w.s0, i * cap, lens[i], cap)
+                                           for i, w in enumerate(rows)])
+            if noise is not None:
+                ops.copy_windows(noise, noise_rows, [(w.a, i * C * wf, w.b - w.a, wf)
+                                                     for i, w in enumerate(rows)],
+                                 channels=C, src_rstride=noise.shape[1], dst_rstride=wf)
+            if self.graph:
+                o, _ = run.replay(m, lens, [src] * m, [tgt] * m)
+            else:
+                pad = self._pad_rows
+                o, _ = self.model.convert_bucketed(
+                    wav_rows, pad(lens, bb, dtype=torch.int32), pad([src] * m, bb, dtype=torch.long),
+                    pad([tgt] * m, bb, dtype=torch.long), noise_rows, wf, stft=stft)
+            ops.copy_windows(o, out, [(i * wf * hop + w.core_off, w.core_lo * hop,
+                                       (w.core_hi - w.core_lo) * hop,
+                                       (w.core_hi - w.core_lo) * hop)
+                                      for i, w in enumerate(rows)])
+        return out
+
+    def convert_long(self, wav, spkid_src, spkid_tgt, *, sampling_rate_in=None, noise_scale=0.0,
+                     window_frames=None, _context=None):
+        """``convert`` for a recording of any length: float32 [(n // hop) *
+        hop], with no seam.  The recording runs as overlapping windows of
+        ``window_frames`` frames (a conversion bucket; default
+        LONG_WINDOW_FRAMES) through the conversion graphs ``convert`` uses,
+        up to MAX_BATCH windows per replay; every window carries
+        SynthesizerTrn.vc_context_frames real frames between an artificial
+        edge and its core, so the cores, stitched on the device, are bit for
+        bit the conversion of the whole recording (an fp16 model at the base
+        config: to fp16 rounding, its decoder depends on a row's start;
+        DESIGN.md 4t).  A recording that fits one window is that window,
+        with the bytes ``convert`` returns at noise_scale 0; noise_scale > 0
+        draws once for the whole recording.  Raises ValueError for a
+        recording of at most (n_fft - hop) / 2 samples or of more than
+        LONG_MAX_SAMPLES, VitsAmdError on a CPU device."""
+        self._vc_begin("convert_long")
+        self._long_check(np.asarray(wav).reshape(-1).shape[0], sampling_rate_in)
+        out, frames = self._convert_windows(wav, spkid_src, spkid_tgt, sampling_rate_in,
+                                            noise_scale, window_frames, _context)
+        return self._to_host(out[0, :frames * self.hop_size])
+
+    def convert_pcm_long(self, wav, spkid_src, spkid_tgt, *, sampling_rate_in=None,
+                         noise_scale=0.0, window_frames=None, pitch=1.0, sampling_rate=None,
+                         volume=1.0, tail_silence=0.0):
+        """convert_long plus the output stage of convert_pcm over the
+        stitched waveform as ONE row of (n // hop) * hop samples; one
+        device-to-host copy, of the int16 PCM.  The output stage carries its
+        lengths as C ints: a recording that exceeds LONG_MAX_SAMPLES samples
+        at the input rate, at the model rate or after a resampling pass
+        (tail included) is refused with ValueError before anything is
+        uploaded.  Returns (pcm int16 [n], n_model_samples)."""
+        self._vc_begin("convert_pcm_long")
+        out = self._output(pitch, sampling_rate, volume, tail_silence)
+        self._long_check(np.asarray(wav).reshape(-1).shape[0], sampling_rate_in, out)
+        w, frames = self._convert_windows(wav, spkid_src, spkid_tgt, sampling_rate_in,
+                                          noise_scale, window_frames, None)
+        n = frames * self.hop_size
+        pcm = self._post(w, out, lengths=n)
+        return self._to_host(pcm[0, :self._n_out(n, out.passes) + out.tail]), n
 
     # -- forced alignment: recording and text in, durations out ---------------------
     # the widest text the alignment kernel takes (vits_maximum_path_durations)

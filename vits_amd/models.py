@@ -307,6 +307,30 @@ class Generator(nn.Module):
     def infer(self, x, g):
         return self.forward(x, g)
 
+    def context_frames(self):
+        """Input frames on each side of frame f that its hop output samples
+        can depend on, from the modules' own kernels, dilations, strides and
+        paddings, exactly and in integers: the interval of samples [0, hop)
+        is taken backwards through conv_post, every stage's longest ResBlock2
+        branch (per pair c1, dilated, and c2), every transposed conv (output
+        t reads the inputs i with 0 <= t + p - i * u < k) and conv_pre."""
+        def reach(conv):
+            return (conv.kernel_size[0] - 1) // 2 * conv.dilation[0]
+
+        hop = 1
+        for up in self.ups:
+            hop *= up.stride[0]
+        lo, hi = -reach(self.conv_post), hop - 1 + reach(self.conv_post)
+        for i in reversed(range(self.num_upsamples)):
+            rbs = self.resblocks[i * self.num_kernels:(i + 1) * self.num_kernels]
+            r = max(sum(reach(c1) + reach(c2) for c1, c2 in zip(rb.convs1, rb.convs2))
+                    for rb in rbs)
+            up = self.ups[i]
+            k, u, p = up.kernel_size[0], up.stride[0], up.padding[0]
+            lo, hi = -((k - 1 - p - (lo - r)) // u), (hi + r + p) // u  # (ceil, floor)
+        lo, hi = lo - reach(self.conv_pre), hi + reach(self.conv_pre)
+        return max(-lo, hi, 0)
+
 
 def _control_buffers(static, batch, t_x, dev):
     """The static control buffers of a captured infer_bucketed(control=...),
@@ -934,6 +958,32 @@ class SynthesizerTrn(nn.Module):
             y.dtype)
         return o.to(y.dtype), y_mask, tuple(t.to(y.dtype) for t in zs)
 
+    def vc_context_frames(self, stft):
+        """Frames on each side of a frame that can influence its converted
+        samples (``stft`` as convert_bucketed takes it): a window of a long
+        recording with this many real frames between an artificial edge and
+        its core reproduces the whole recording's samples on that core.  The
+        audio side is local in time, so the parts add up:
+          - the STFT: frames at a row's ends whose support [j * hop - pad,
+            j * hop - pad + n_fft) leaves the row and sees reflected samples;
+          - enc_q: its WN stack, sum_i (k - 1) / 2 * dilation_rate ** i (the
+            1x1 convs and the channel LayerNorm add nothing);
+          - the flow, forward and reverse: every coupling's WN stack, twice;
+          - the decoder: Generator.context_frames."""
+        n_fft, hop, _ = (int(v) for v in stft)
+        if hop != self.hop_total:
+            raise ValueError(f"vc_context_frames: hop {hop} is not the decoder's {self.hop_total}")
+        pad = (n_fft - hop) // 2
+
+        def wn(m):
+            k = m.kernel_size[0]
+            return sum((k - 1) // 2 * m.dilation_rate ** i for i in range(m.n_layers))
+
+        edge = max(-(-pad // hop), -(-(n_fft - pad) // hop) - 1)
+        flow = sum(wn(f.enc) for f in self.flow.flows
+                   if isinstance(f, modules.ResidualCouplingLayer))
+        return edge + wn(self.enc_q.enc) + 2 * flow + self.dec.context_frames()
+
     def _vc_window(self, win, dev):
         w = self.__dict__.get("_vc_win")
         if w is None or w.numel() != win or w.device != dev:
@@ -973,7 +1023,13 @@ class SynthesizerTrn(nn.Module):
         buffers: wav [n, <= t_y * hop + hop - 1] fp32 rows, n_samples /
         sid_src / sid_tgt n host ints (or tensors), noise [n, C, t_y] or None
         (the static noise is then zeroed: the posterior mean).  Rows at or
-        past n get length 0."""
+        past n get length 0.
+
+        ``run.replay(n, n_samples, sid_src, sid_tgt)`` is the same replay for
+        a caller that has written the rows of ``run.static["wav"]`` [batch,
+        t_y * hop + hop - 1] and ``run.static["noise"]`` [batch, C, t_y]
+        itself (ops.copy_windows of a long recording: no staging tensor and
+        no second copy); it touches neither buffer."""
         dev = next(self.parameters()).device
         n_fft, hop, win = (int(v) for v in stft)
         t_y, batch = int(t_y), int(batch)
@@ -993,23 +1049,28 @@ class SynthesizerTrn(nn.Module):
         graph, out = self._capture_body(body, warmup, dev)
         _ints = self._row_ints
 
+        def replay(n, n_samples, sid_src, sid_tgt):
+            if not 1 <= n <= batch:
+                raise ValueError(f"convert replay: {n} rows do not fit a batch of {batch}")
+            _fill_rows(static["n"], _ints(n_samples, n, torch.int32), n)
+            _fill_rows(static["src"], _ints(sid_src, n, torch.long), n)
+            _fill_rows(static["tgt"], _ints(sid_tgt, n, torch.long), n)
+            graph.replay()
+            return out
+
         def run(wav, n_samples, sid_src, sid_tgt, noise=None):
             n = wav.shape[0]
             if not 1 <= n <= batch or wav.shape[1] > cap:
                 raise ValueError(f"convert replay: wav {tuple(wav.shape)} does not fit "
                                  f"[{batch}, {cap}]")
             static["wav"][:n, :wav.shape[1]].copy_(wav)
-            _fill_rows(static["n"], _ints(n_samples, n, torch.int32), n)
-            _fill_rows(static["src"], _ints(sid_src, n, torch.long), n)
-            _fill_rows(static["tgt"], _ints(sid_tgt, n, torch.long), n)
             if noise is None:
                 static["noise"].zero_()
             else:
                 static["noise"][:n].copy_(noise)
-            graph.replay()
-            return out
+            return replay(n, n_samples, sid_src, sid_tgt)
 
-        return self._graph_run(run, graph, static, t_y=t_y, batch=batch)
+        return self._graph_run(run, graph, static, t_y=t_y, batch=batch, replay=replay)
 
     @staticmethod
     def _row_ints(v, n, dtype):

@@ -2073,3 +2073,37 @@ def pack_pcm_rows(rows: torch.Tensor, y_len: torch.Tensor, hop: int, passes_per_
         down, (C.c_int32 * B)(*tails), nr_ptr, B, offsets.data_ptr(), stream.data_ptr(),
         stream.numel(), _stream_ptr(rows.device)), "vits_pack_pcm_rows")
     return out, offsets, stream
+
+
+# -- window copy: the gathers and the scatter of long-recording conversion ------
+
+COPY_MAX_JOBS = 64  # window.hip CW_MAX_JOBS
+
+
+def copy_windows(src: torch.Tensor, dst: torch.Tensor, jobs, *, channels: int = 1,
+                 src_rstride: int = 0, dst_rstride: int = 0) -> torch.Tensor:
+    """Ranges of fp32 elements from ``src`` into ``dst``, both contiguous and
+    addressed flat (element offsets into their storage as laid out): for
+    every job (src_off, dst_off, len, fill_len) and channel r < ``channels``,
+    dst[dst_off + r * dst_rstride + i] = src[src_off + r * src_rstride + i]
+    for i < len and 0 for len <= i < fill_len; nothing else is written.  64
+    jobs are one launch (more: one launch per 64); the jobs travel in the
+    kernel arguments, so the call makes no copy, allocates nothing and can be
+    captured.  A job that leaves either tensor is refused.  Returns dst."""
+    what = "copy_windows"
+    require_device(src, dst)
+    for name, t in (("src", src), ("dst", dst)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.VitsAmdError(f"{what}: {name} must be a contiguous fp32 tensor")
+    jobs = [tuple(int(v) for v in j) for j in jobs]
+    if any(len(j) != 4 for j in jobs):
+        raise _lib.VitsAmdError(f"{what}: a job is (src_off, dst_off, len, fill_len)")
+    lib = _lib.load()
+    for lo in range(0, len(jobs), COPY_MAX_JOBS):
+        part = jobs[lo:lo + COPY_MAX_JOBS]
+        table = (_lib.WindowJob * len(part))(*[_lib.WindowJob(*j) for j in part])
+        check(lib.vits_copy_windows(
+            src.data_ptr(), src.numel(), int(src_rstride), dst.data_ptr(), dst.numel(),
+            int(dst_rstride), table, len(part), int(channels), _stream_ptr(src.device)),
+            "vits_copy_windows")
+    return dst

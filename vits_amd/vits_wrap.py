@@ -259,8 +259,9 @@ class VITSWrap(object):
         ``speaking`` without its text fields: "wav" (RIFF bytes), "sr",
         "segment_info" (one entry, start_ms / end_ms), the times and rtf.
         Clamps as in ``speaking``.  Needs device_post=True: the recording is
-        converted and post-processed on the GPU (EmoVITS.convert_pcm) and only
-        the int16 PCM comes back."""
+        converted and post-processed on the GPU (EmoVITS.convert_pcm; a
+        recording of more than 4096 frames: convert_pcm_long, seamless
+        windows) and only the int16 PCM comes back."""
         if not self.device_post:
             raise ValueError("VITSWrap.converting needs device_post=True on a ROCm GPU")
         volume = max(0.0, min(1.0, float(inputs.get("volume", self.default_volume))))
@@ -271,7 +272,12 @@ class VITSWrap(object):
         inputs.setdefault("id", str(time.time()).replace(".", "_"))
         spkid_tgt = int(inputs.get("spkid_tgt", self.default_spkid))
         t0 = time.time()
-        pcm, n_model = self.speecher.convert_pcm(
+        # a recording past the largest conversion bucket runs as seamless windows
+        ev = self.speecher
+        frames = ev._vc_lengths(np.asarray(inputs["wav"]).reshape(-1).shape[0],
+                                inputs.get("sampling_rate_in"))[2]
+        convert = ev.convert_pcm_long if frames > ev.VC_MAX_FRAMES else ev.convert_pcm
+        pcm, n_model = convert(
             inputs["wav"], int(inputs["spkid_src"]), spkid_tgt,
             sampling_rate_in=inputs.get("sampling_rate_in"), pitch=pitch,
             sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence)
