@@ -404,6 +404,56 @@ int vits_maximum_path_durations(const float* neg_cent, const int32_t* t_t_len,
                                 int32_t* frame_token, int batch, int t_t, int t_s,
                                 void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Forced alignment of long recordings: the DP, backtrack and reductions of  */
+/* vits_maximum_path_durations, bit for bit, over a score matrix that is fed */
+/* in panels of `panel` frames (a multiple of 32) by all t_s tokens and is   */
+/* never held as a whole; t_s has no limit.  A panel's row is processed in   */
+/* strips of `strip` tokens (64 * 2^k, k <= 5).  The sequence of one job, on */
+/* one stream:                                                               */
+/*   vits_mas_long_panel      for y0 = 0, panel, 2 panel, ... in this order  */
+/*   vits_mas_long_backtrack  durations and frame_token (or NULL)            */
+/*   vits_mas_long_gather     for every panel again, in any order (scores)   */
+/*   vits_mas_long_scores     the per-token sums                             */
+/* `scores` of _panel / _gather points at row y0 of the matrix: [batch] x    */
+/* [rows][t_s] fp32, `batch_stride` elements from one recording to the next  */
+/* (>= rows * t_s).  rows <= panel, and rows < panel only for the last       */
+/* panel (y0 + rows == t_t).  The gather must see the same values as the     */
+/* forward step.  t_t_len / t_s_len, the outputs and the rows without an     */
+/* alignment are those of vits_maximum_path_durations; all five calls of a   */
+/* job take the same batch, t_t, t_s, strip, panel and workspace.  The       */
+/* workspace holds the job's state between the calls, in sections rounded up */
+/* to 256 bytes each, with Ws = ceil(t_s / strip) * strip:                   */
+/*   float    carry[2][batch][Ws]               V[y0 - 1][.]: a panel reads  */
+/*                                              half (y0 / panel) & 1 and    */
+/*                                              writes the other             */
+/*   uint32_t words[batch][ceil(t_t / 32)][Ws]  decision bits, bit y mod 32  */
+/*   int32_t  frame_token[batch][t_t]                                        */
+/*   int32_t  start[batch][Ws + 1]              first frame of every token   */
+/*   float    val[batch][t_t]                   the path's own scores        */
+/* It needs no initialisation and must be 16-byte aligned.  The calls are    */
+/* asynchronous and capture-safe and depend on each other through stream     */
+/* order alone.  Each returns VITS_E_ARG, before any launch, for a null      */
+/* pointer (frame_token excepted), a non-positive size, a panel that is no   */
+/* multiple of 32, a strip that is not 64 * 2^k with k <= 5, a y0 that is    */
+/* negative, no multiple of panel or >= t_t, rows outside the above, or a    */
+/* workspace of fewer than vits_mas_long_workspace bytes; VITS_E_UNSUP for a */
+/* panel whose column buffers do not fit the LDS beside the strip's ring.    */
+/* vits_mas_long_workspace returns 0 for sizes the calls would refuse.       */
+int64_t vits_mas_long_workspace(int batch, int t_t, int t_s, int strip, int panel);
+int vits_mas_long_panel(const float* scores, int64_t batch_stride, const int32_t* t_t_len,
+                        const int32_t* t_s_len, int batch, int t_t, int t_s, int strip, int panel,
+                        int y0, int rows, void* workspace, int64_t workspace_bytes, void* stream);
+int vits_mas_long_backtrack(const int32_t* t_t_len, const int32_t* t_s_len, int32_t* durations,
+                            int32_t* frame_token, int batch, int t_t, int t_s, int strip,
+                            int panel, void* workspace, int64_t workspace_bytes, void* stream);
+int vits_mas_long_gather(const float* scores, int64_t batch_stride, const int32_t* t_t_len,
+                         const int32_t* t_s_len, int batch, int t_t, int t_s, int strip,
+                         int panel, int y0, int rows, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+int vits_mas_long_scores(const int32_t* t_t_len, const int32_t* t_s_len, float* token_scores,
+                         int batch, int t_t, int t_s, int strip, int panel, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------- */
 /* MAS scores (models.py:483-490): neg_cent[b][y][x] = sum_d(-0.5 log 2pi */
 /* - logs_p - 0.5 z_p^2 s + z_p m_p s - 0.5 m_p^2 s), s = exp(-2 logs_p). */

@@ -375,6 +375,21 @@ _SIGS = {
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
          C.c_int, C.c_void_p, C.c_int64, C.c_void_p],
     ),
+    "vits_mas_long_workspace": (C.c_int64, [C.c_int] * 5),
+    "vits_mas_long_panel": (
+        C.c_int,
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 7
+        + [C.c_void_p, C.c_int64, C.c_void_p],
+    ),
+    "vits_mas_long_backtrack": (
+        C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "vits_mas_long_gather": (
+        C.c_int,
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 7
+        + [C.c_void_p, C.c_int64, C.c_void_p],
+    ),
+    "vits_mas_long_scores": (
+        C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p, C.c_int64, C.c_void_p]),
     "vits_stft_mag_forward_multi": (C.c_int, [C.POINTER(StftJob), C.c_int, C.c_void_p]),
     "vits_stft_mag_backward_multi": (
         C.c_int, [C.POINTER(StftJob), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),

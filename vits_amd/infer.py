@@ -1287,6 +1287,202 @@ class EmoVITS(object):
                                     sampling_rate_in, noise_scale)
         return out
 
+    # -- forced alignment of long recordings: many segments, any length
+    # the caps of align_long: the total tokens of a text (a 40-minute reading
+    # at 1 token per 6 frames), and the bytes of the search's workspace plus
+    # one panel of scores (at the token cap: a recording of 78 minutes)
+    ALIGN_LONG_MAX_TOKENS = 32768
+    ALIGN_LONG_MAX_BYTES = 2 ** 31
+    ALIGN_LONG_PANEL_FRAMES = 4096
+    ALIGN_LONG_STRIP_TOKENS = 2048
+
+    def _align_long_bytes(self, frames, tokens, strip, panel):
+        """Device bytes of the long search at [frames, tokens]: the workspace
+        of vits_mas_long_* (the decision words, frames * tokens / 8, and a few
+        vectors) plus one panel of scores; (bytes, strip, panel as run)."""
+        strip, panel = ops.mas_long_plan(frames, tokens, strip, panel)
+        ws = int(ops._lib.load().vits_mas_long_workspace(1, frames, tokens, strip, panel))
+        if ws <= 0:
+            raise ValueError(f"no long alignment plan for {frames} frames x {tokens} tokens at "
+                             f"strips of {strip} and panels of {panel}")
+        return ws + 4 * panel * tokens, strip, panel
+
+    def _align_long_check(self, n_in, sampling_rate_in, tokens, window_frames, panel_frames,
+                          strip_tokens):
+        """Everything align_long refuses, from host arithmetic alone, before
+        anything is uploaded: (frames, window frames, strip, panel)."""
+        if len(tokens) == 0:
+            raise ValueError("align_long: no text segment")
+        for i, t in enumerate(tokens):
+            if t < 1:
+                raise ValueError(f"align_long: segment {i} is empty")
+        total = sum(tokens)
+        frames = self._long_check(n_in, sampling_rate_in)
+        if frames < total:
+            raise ValueError(f"recording of {frames} frames cannot be aligned with {total} "
+                             "tokens: every token takes at least one frame")
+        if total > self.ALIGN_LONG_MAX_TOKENS:
+            raise ValueError(f"text of {total} tokens exceeds align_long's "
+                             f"{self.ALIGN_LONG_MAX_TOKENS}")
+        wf = self.LONG_WINDOW_FRAMES if window_frames is None else int(window_frames)
+        if not self.VC_MIN_FRAMES <= wf <= self.VC_MAX_FRAMES or self._frame_bucket(wf) != wf:
+            raise ValueError(f"window_frames must be a conversion bucket (a power of two, "
+                             f"{self.VC_MIN_FRAMES} .. {self.VC_MAX_FRAMES}), got {wf}")
+        strip = self.ALIGN_LONG_STRIP_TOKENS if strip_tokens is None else int(strip_tokens)
+        panel = self.ALIGN_LONG_PANEL_FRAMES if panel_frames is None else int(panel_frames)
+        if strip not in ops.MAS_LONG_STRIPS:
+            raise ValueError(f"strip_tokens must be one of {ops.MAS_LONG_STRIPS}, got {strip}")
+        if panel < 32 or panel % 32:
+            raise ValueError(f"panel_frames must be a positive multiple of 32, got {panel}")
+        need, strip, panel = self._align_long_bytes(frames, total, strip, panel)
+        if need > self.ALIGN_LONG_MAX_BYTES:
+            raise ValueError(f"aligning {frames} frames with {total} tokens takes {need} bytes of "
+                             f"workspace, above align_long's {self.ALIGN_LONG_MAX_BYTES}")
+        return frames, wf, strip, panel
+
+    def _latent_windows(self, x, plan, wf, sid, noise=None):
+        """z_p fp32 [1, C, F] of the recording x (fp32 [n] on the device)
+        through the windows ``plan`` as rows of ``wf`` frames: _run_windows'
+        gathers (waveform, and the rows' slices of ``noise`` fp32 [C, F]) into
+        the static buffers of the graph cached under ("latents", batch
+        bucket, wf), a replay, and one ops.copy_windows that scatters the
+        cores' columns into their places (R = channels).  graph=False: the
+        same gathers into fresh tensors and latents_bucketed eagerly.  No
+        host sync."""
+        stft = self._vc_stft()
+        hop = stft[1]
+        F = x.numel() // hop
+        C, cap = self.inter_channels, wf * hop + hop - 1
+        out = torch.empty(1, C, F, device=self.device)
+        for lo, hi in self._groups(len(plan)):
+            rows = plan[lo:hi]
+            m = len(rows)
+            bb = 1 if m == 1 else self._batch_bucket(m)
+            lens = [w.s1 - w.s0 for w in rows]
+            if self.graph:
+                run = self._cached_graph(
+                    ("latents", bb, wf),
+                    lambda: self.model.capture_latents_bucketed(wf, batch=bb, stft=stft))
+                wav_rows, noise_rows = run.static["wav"], run.static["noise"]
+                if noise is None:
+                    noise_rows.zero_()
+            else:
+                wav_rows = torch.zeros(bb, cap, device=self.device)
+                noise_rows = None if noise is None else torch.zeros(bb, C, wf, device=self.device)
+            ops.copy_windows(x, wav_rows, [(w.s0, i * cap, lens[i], cap)
+                                           for i, w in enumerate(rows)])
+            if noise is not None:
+                ops.copy_windows(noise, noise_rows, [(w.a, i * C * wf, w.b - w.a, wf)
+                                                     for i, w in enumerate(rows)],
+                                 channels=C, src_rstride=noise.shape[1], dst_rstride=wf)
+            if self.graph:
+                z, _ = run.replay(m, lens, [sid] * m)
+            else:
+                pad = self._pad_rows
+                z, _ = self.model.latents_bucketed(
+                    wav_rows, pad(lens, bb, dtype=torch.int32), pad([sid] * m, bb, dtype=torch.long),
+                    noise_rows, wf, stft=stft)
+            ops.copy_windows(z, out, [(i * C * wf + w.core_lo - w.a, w.core_lo,
+                                       w.core_hi - w.core_lo, w.core_hi - w.core_lo)
+                                      for i, w in enumerate(rows)],
+                             channels=C, src_rstride=wf, dst_rstride=F)
+        return out
+
+    @torch.no_grad()
+    def _segment_priors(self, texts, tokens, sids, emos):
+        """m_p, logs_p fp32 [1, C, sum(tokens)] of the segments, each encoded
+        on its own (pad_exact) with its own emotion vector, in groups of up
+        to MAX_BATCH at the text buckets; each row's exact-length columns are
+        gathered into their place with ops.copy_windows.  No host sync."""
+        C, total = self.inter_channels, sum(tokens)
+        m_all = torch.empty(1, C, total, device=self.device)
+        l_all = torch.empty(1, C, total, device=self.device)
+        offs = np.concatenate([[0], np.cumsum(tokens)])
+        pad = self._pad_rows
+        for lo, hi in self._groups(len(texts)):
+            m = hi - lo
+            bb = 1 if m == 1 else self._batch_bucket(m)
+            tk = tokens[lo:hi]
+            xb = self._text_bucket(max(tk))
+            x = pad(self._text_rows(texts[lo:hi], tk), bb, xb)
+            emo = pad(torch.cat(emos[lo:hi]), bb)
+            g = self.model.emb_g(pad(sids[lo:hi], bb, dtype=torch.long))
+            _, m_p, logs_p = self.model.enc_p.forward_masked_hip(
+                x, pad(tk, bb, dtype=torch.int32), emo, g, pad_exact=True)
+            jobs = [(i * C * xb, int(offs[lo + i]), tk[i], tk[i]) for i in range(m)]
+            for src, dst in ((m_p, m_all), (logs_p, l_all)):
+                ops.copy_windows(src.float().contiguous(), dst, jobs, channels=C, src_rstride=xb,
+                                 dst_rstride=total)
+        return m_all, l_all
+
+    def align_long(self, wav, spkid, texts, emos, *, sampling_rate_in=None, noise_scale=0.0,
+                   window_frames=None, panel_frames=None, strip_tokens=None, _context=None,
+                   _keep=None):
+        """``align`` for a recording of any length against a text in any
+        number of segments: ``texts`` a list of [Tx_i, c], ``emos`` one
+        emotion per segment (as ``infer`` takes them), each segment encoded on
+        its own as ``infer_batch`` feeds the model, the concatenated text
+        aligned with the whole recording by one exact global search
+        (SynthesizerTrn.align_segments is the definition).  Returns
+        (durations: a list of int32 arrays, one per segment; scores:
+        likewise, float32; segment_frames int64 [n_seg + 1]: the frame at
+        which each segment starts, cumulative, ending at ``frames``; frames).
+
+        z_p of the recording comes from overlapping windows of
+        ``window_frames`` frames (a conversion bucket; default
+        LONG_WINDOW_FRAMES) with SynthesizerTrn.align_context_frames of
+        context, up to MAX_BATCH per replay of a graph cached under
+        ("latents", batch bucket, window_frames); the search
+        (ops.maximum_path_durations_long) takes it in panels of
+        ``panel_frames`` frames (default 4096) and strips of ``strip_tokens``
+        tokens (default 2048) and never holds the score matrix.  One
+        device-to-host copy at the end, no sync before it.  noise_scale > 0
+        draws once for the whole recording.  Raises ValueError, before
+        anything is uploaded, for an empty segment, fewer frames than total
+        tokens, more than ALIGN_LONG_MAX_TOKENS tokens, a workspace above
+        ALIGN_LONG_MAX_BYTES and what convert_long refuses; VitsAmdError on a
+        CPU device."""
+        stft = self._vc_begin("align_long")
+        texts = [np.ascontiguousarray(t) for t in texts]
+        emos = list(emos)
+        if len(emos) != len(texts):
+            raise ValueError(f"align_long: {len(texts)} segments need {len(texts)} emotions, got "
+                             f"{len(emos)}")
+        tokens = [int(t.shape[0]) for t in texts]
+        F, wf, strip, panel = self._align_long_check(
+            np.asarray(wav).reshape(-1).shape[0], sampling_rate_in, tokens, window_frames,
+            panel_frames, strip_tokens)
+        resolved = [self._resolve(spkid, e) for e in emos]
+        sids = [int(s) for s, _ in resolved]
+        x, F2, _ = self._vc_input(wav, sampling_rate_in, capped=False)
+        assert F2 == F
+        if F <= wf:
+            plan = [_Window(0, F, 0, F, 0, x.numel(), 0)]
+        else:
+            ctx = self.model.align_context_frames(stft) if _context is None else int(_context)
+            plan = self._long_plan(x.numel(), wf, ctx)
+        noise = None
+        if noise_scale > 0:
+            if self._vc_gen is None:
+                self._vc_gen = torch.Generator(device=self.device)
+            noise = torch.randn(self.inter_channels, F, device=self.device,
+                                generator=self._vc_gen) * float(noise_scale)
+        z_p = self._latent_windows(x, plan, wf, sids[0], noise)
+        m_p, logs_p = self._segment_priors(texts, tokens, sids, [e for _, e in resolved])
+        total = sum(tokens)
+        lens = torch.tensor([F, total], dtype=torch.int32).to(self.device)
+        dur, scores, _ = ops.maximum_path_durations_long(z_p, m_p, logs_p, lens[:1], lens[1:],
+                                                         strip=strip, panel=panel)
+        if _keep is not None:  # (tests: the latents on the device)
+            _keep.update(z_p=z_p, m_p=m_p, logs_p=logs_p)
+        host = self._to_host(torch.cat([dur[0], scores[0].view(torch.int32)]))
+        d, s = host[:total], host[total:].view(np.float32)
+        offs = np.concatenate([[0], np.cumsum(tokens)])
+        seg_frames = np.concatenate([[0], np.cumsum(d, dtype=np.int64)[offs[1:] - 1]])
+        return ([d[offs[i]:offs[i + 1]].copy() for i in range(len(tokens))],
+                [s[offs[i]:offs[i + 1]].copy() for i in range(len(tokens))],
+                seg_frames.astype(np.int64), F)
+
     # text tokens are padded to a multiple of TX_BUCKET (masked encoder);
     # frame buckets are powers of two from 256 up to the noise buffer's 4096
     TX_BUCKET = 32

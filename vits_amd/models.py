@@ -1116,6 +1116,120 @@ class SynthesizerTrn(nn.Module):
         x_len = x_lengths.to(device=dev, dtype=torch.int32).contiguous()
         return self._align_core(engine._f32(y).contiguous(), noise, y_len, x, x_len, emo, sid)
 
+    def align_context_frames(self, stft):
+        """Frames on each side of a frame that can influence its z_p (``stft``
+        as convert_bucketed takes it): the context a window of a long
+        recording needs so that z_p on its core is the whole recording's.  The
+        parts of vc_context_frames with the flow counted once (forward only)
+        and no decoder: the STFT's edge frames, enc_q's WN stack and every
+        coupling's WN stack."""
+        n_fft, hop, _ = (int(v) for v in stft)
+        if hop != self.hop_total:
+            raise ValueError(f"align_context_frames: hop {hop} is not the decoder's "
+                             f"{self.hop_total}")
+        pad = (n_fft - hop) // 2
+
+        def wn(m):
+            k = m.kernel_size[0]
+            return sum((k - 1) // 2 * m.dilation_rate ** i for i in range(m.n_layers))
+
+        edge = max(-(-pad // hop), -(-(n_fft - pad) // hop) - 1)
+        flow = sum(wn(f.enc) for f in self.flow.flows
+                   if isinstance(f, modules.ResidualCouplingLayer))
+        return edge + wn(self.enc_q.enc) + flow
+
+    @torch.no_grad()
+    def align_segments(self, xs, emos, y, y_length, sid, noise=None):
+        """Forced alignment of ONE recording with a text in segments: the
+        linear spectrogram y [1, F, Ty] (y_length frames) of speaker sid
+        against the segments xs (a list of [Tx_i, c]), each encoded on its own
+        with its own emotion vector (emos: a list of [1024]), as ``speaking``
+        feeds the model; m_p / logs_p of the segments are concatenated along
+        the tokens and searched as one text.  Exact-length and eager: the
+        definition EmoVITS.align_long is held to.  Up to 2048 tokens in all
+        the search is ``align``'s (ops.neg_cent and maximum_path_durations);
+        above, ops.maximum_path_durations_long, which equals it bit for bit
+        wherever both run.  Returns (durations int32 [Tx_total], scores fp32
+        [Tx_total], segment token offsets (a list of n + 1 ints, cumulative),
+        (z_p [1, C, Ty], m_p, logs_p [1, C, Tx_total]) in fp32)."""
+        engine._check_gpu(y, "SynthesizerTrn.align_segments")
+        if len(xs) == 0 or len(xs) != len(emos):
+            raise ValueError(f"align_segments: {len(xs)} segments and {len(emos)} emotion vectors")
+        dev = y.device
+        y = y if y.dim() == 3 else y[None]
+        sid = torch.as_tensor(sid, device=dev, dtype=torch.long).reshape(1)
+        g = self.emb_g(sid)
+        ms, ls, offs = [], [], [0]
+        for x, emo in zip(xs, emos):
+            x = x.reshape(1, -1, self.text_channels)
+            n = x.shape[1]
+            if n == 0:
+                raise ValueError("align_segments: an empty segment")
+            x_len = torch.full((1,), n, device=dev, dtype=torch.int32)
+            _, m, lg = self.enc_p.forward_masked_hip(x, x_len, emo.reshape(1, -1), g,
+                                                     pad_exact=True)
+            ms.append(engine._f32(m))
+            ls.append(engine._f32(lg))
+            offs.append(offs[-1] + n)
+        m_p, logs_p = torch.cat(ms, dim=2), torch.cat(ls, dim=2)
+        y_len = torch.as_tensor(y_length, dtype=torch.int32).reshape(1).to(dev)
+        _, z_p, _ = self._audio_latents(engine._f32(y).contiguous(), noise, y_len, engine._f32(g))
+        t_s = torch.full((1,), offs[-1], device=dev, dtype=torch.int32)
+        if offs[-1] <= 2048:
+            dur, scores, _ = engine.ops.maximum_path_durations(
+                engine.ops.neg_cent(z_p, m_p, logs_p), y_len, t_s)
+        else:
+            dur, scores, _ = engine.ops.maximum_path_durations_long(z_p, m_p, logs_p, y_len, t_s)
+        return dur[0], scores[0], offs, (z_p, m_p, logs_p)
+
+    @torch.no_grad()
+    def latents_bucketed(self, wav, n_samples, sid, noise, t_y, *, stft):
+        """The audio side of align_bucketed alone, with NO host
+        synchronisation, over a static bucket of t_y frames: wav, n_samples,
+        noise and ``stft`` as convert_bucketed takes them, sid [B] the rows'
+        speakers.  Returns (z_p fp32 [B, C, t_y], y_len int32 [B]): the first
+        y_len[b] frames of row b are z_p of that row alone at its exact
+        length, the rest is zero."""
+        engine._check_gpu(wav, "SynthesizerTrn.latents_bucketed")
+        spec, y_len = self._spec_rows("latents_bucketed", wav, n_samples, int(t_y), stft)
+        with engine.ops.length_skip(64):
+            _, z_p, _ = self._audio_latents(spec, noise, y_len, engine._f32(self.emb_g(sid)))
+        return z_p, y_len
+
+    @torch.no_grad()
+    def capture_latents_bucketed(self, t_y, batch=1, warmup=2, *, stft):
+        """One hipGraph for latents_bucketed over [batch, t_y] (``stft`` as
+        there).  Returns run with ``run.static`` (wav [batch, t_y * hop + hop
+        - 1], noise [batch, C, t_y], which the caller fills: ops.copy_windows
+        of a long recording) and ``run.replay(n, n_samples, sid)`` -> (z_p
+        [batch, C, t_y], y_len [batch]), views of static buffers; rows at or
+        past n get length 0."""
+        dev = next(self.parameters()).device
+        n_fft, hop, win = (int(v) for v in stft)
+        t_y, batch = int(t_y), int(batch)
+        static = dict(wav=torch.zeros(batch, t_y * hop + hop - 1, device=dev),
+                      n=torch.zeros(batch, device=dev, dtype=torch.int32),
+                      sid=torch.zeros(batch, device=dev, dtype=torch.long),
+                      noise=torch.zeros(batch, self.inter_channels, t_y, device=dev))
+        self._vc_window(win, dev)  # (built outside the capture)
+
+        def body():
+            return self.latents_bucketed(static["wav"], static["n"], static["sid"],
+                                         static["noise"], t_y, stft=(n_fft, hop, win))
+
+        graph, out = self._capture_body(body, warmup, dev)
+        _ints = self._row_ints
+
+        def replay(n, n_samples, sid):
+            if not 1 <= n <= batch:
+                raise ValueError(f"latents replay: {n} rows do not fit a batch of {batch}")
+            _fill_rows(static["n"], _ints(n_samples, n, torch.int32), n)
+            _fill_rows(static["sid"], _ints(sid, n, torch.long), n)
+            graph.replay()
+            return out
+
+        return self._graph_run(replay, graph, static, t_y=t_y, batch=batch, replay=replay)
+
     @torch.no_grad()
     def align_bucketed(self, wav, n_samples, x, x_lengths, emo, sid, noise, t_x, t_y, *, stft):
         """align from the waveform with NO host synchronisation, over a

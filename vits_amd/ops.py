@@ -1543,6 +1543,153 @@ def maximum_path_durations(neg_cent: torch.Tensor, t_t: torch.Tensor, t_s: torch
     return dur, sc, ft
 
 
+MAS_LONG_STRIPS = (64, 128, 256, 512, 1024, 2048)
+
+
+def mas_long_plan(Tt: int, Ts: int, strip: int, panel: int) -> tuple[int, int]:
+    """(strip, panel) the long MAS runs a [Tt, Ts] job at: the asked-for ones,
+    shrunk to the narrowest strip that still holds Ts and to Tt rounded up to
+    whole decision words where the job is smaller than one strip / panel."""
+    strip, panel = int(strip), int(panel)
+    if strip not in MAS_LONG_STRIPS:
+        raise _lib.VitsAmdError(f"maximum_path_durations_long: strip {strip} not in "
+                                f"{MAS_LONG_STRIPS}")
+    if panel <= 0 or panel % 32:
+        raise _lib.VitsAmdError(f"maximum_path_durations_long: panel {panel} is no positive "
+                                "multiple of 32")
+    strip = min(strip, next(s for s in MAS_LONG_STRIPS if s >= min(Ts, MAS_LONG_STRIPS[-1])))
+    panel = min(panel, (Tt + 31) // 32 * 32)
+    return strip, panel
+
+
+class _MasLongJob:
+    """Allocation and launches of one long MAS job (vits_mas_long_*)."""
+
+    def __init__(self, what, B, Tt, Ts, t_t, t_s, strip, panel, scores, frame_token, device):
+        self.what = what
+        self.lib = _lib.load()
+        self.B, self.Tt, self.Ts = B, Tt, Ts
+        self.strip, self.panel = mas_long_plan(Tt, Ts, strip, panel)
+        self.tt = t_t.to(torch.int32).contiguous()
+        self.ts = t_s.to(torch.int32).contiguous()
+        if self.tt.numel() != B or self.ts.numel() != B:
+            raise _lib.VitsAmdError(f"{what}: {B} rows need {B} lengths, got {self.tt.numel()} "
+                                    f"and {self.ts.numel()}")
+        wsb = int(self.lib.vits_mas_long_workspace(B, Tt, Ts, self.strip, self.panel))
+        if wsb <= 0:
+            raise _lib.VitsAmdError(f"{what}: no plan for [{B}, {Tt}, {Ts}] at strip "
+                                    f"{self.strip}, panel {self.panel}")
+        self.ws = torch.empty(wsb, device=device, dtype=torch.uint8)
+        self.dur = torch.empty(B, Ts, device=device, dtype=torch.int32)
+        self.sc = torch.empty(B, Ts, device=device, dtype=torch.float32) if scores else None
+        self.ft = torch.empty(B, Tt, device=device, dtype=torch.int32) if frame_token else None
+        self.stream = _stream_ptr(device)
+
+    def panels(self):
+        return [(y0, min(self.panel, self.Tt - y0)) for y0 in range(0, self.Tt, self.panel)]
+
+    def _dims(self):
+        return (self.B, self.Tt, self.Ts, self.strip, self.panel)
+
+    def _tail(self):
+        return (self.ws.data_ptr(), self.ws.numel(), self.stream)
+
+    def forward(self, ptr, bstride, y0, rows):
+        check(self.lib.vits_mas_long_panel(ptr, bstride, self.tt.data_ptr(), self.ts.data_ptr(),
+                                           *self._dims(), y0, rows, *self._tail()),
+              "vits_mas_long_panel")
+
+    def backtrack(self):
+        check(self.lib.vits_mas_long_backtrack(self.tt.data_ptr(), self.ts.data_ptr(),
+                                               self.dur.data_ptr(), _ptr(self.ft), *self._dims(),
+                                               *self._tail()), "vits_mas_long_backtrack")
+
+    def gather(self, ptr, bstride, y0, rows):
+        check(self.lib.vits_mas_long_gather(ptr, bstride, self.tt.data_ptr(), self.ts.data_ptr(),
+                                            *self._dims(), y0, rows, *self._tail()),
+              "vits_mas_long_gather")
+
+    def sums(self):
+        check(self.lib.vits_mas_long_scores(self.tt.data_ptr(), self.ts.data_ptr(),
+                                            self.sc.data_ptr(), *self._dims(), *self._tail()),
+              "vits_mas_long_scores")
+
+    def result(self):
+        return self.dur, self.sc, self.ft
+
+
+def maximum_path_durations_panels(neg_cent: torch.Tensor, t_t: torch.Tensor, t_s: torch.Tensor, *,
+                                  strip: int, panel: int, scores: bool = True,
+                                  frame_token: bool = False):
+    """maximum_path_durations through the kernels of the long search
+    (vits_mas_long_*): the materialised neg_cent [B, Tt, Ts] fp32 is fed
+    ``panel`` frames at a time and searched in strips of ``strip`` tokens, Ts
+    of any size.  Same outputs, bit for bit.  No host sync: capture-safe."""
+    what = "maximum_path_durations_panels"
+    require_device(neg_cent, t_t, t_s)
+    if neg_cent.dim() != 3:
+        raise _lib.VitsAmdError(f"{what}: neg_cent {tuple(neg_cent.shape)}")
+    nc = neg_cent.detach().to(torch.float32).contiguous()
+    B, Tt, Ts = nc.shape
+    job = _MasLongJob(what, B, Tt, Ts, t_t, t_s, strip, panel, scores, frame_token, nc.device)
+    at = lambda y0: nc.data_ptr() + 4 * y0 * Ts
+    for y0, rows in job.panels():
+        job.forward(at(y0), Tt * Ts, y0, rows)
+    job.backtrack()
+    if scores:
+        for y0, rows in job.panels():
+            job.gather(at(y0), Tt * Ts, y0, rows)
+        job.sums()
+    return job.result()
+
+
+def maximum_path_durations_long(z_p: torch.Tensor, m_p: torch.Tensor, logs_p: torch.Tensor,
+                                t_t: torch.Tensor, t_s: torch.Tensor, *, strip: int = 2048,
+                                panel: int = 4096, scores: bool = True,
+                                frame_token: bool = False):
+    """Forced alignment from the latents, for recordings and texts of any
+    length: maximum_path_durations(neg_cent(z_p, m_p, logs_p), t_t, t_s) in
+    every bit, without the [B, Tt, Ts] matrix.  z_p [B, C, Tt], m_p / logs_p
+    [B, C, Ts] fp32.  A panel of ``panel`` frames of z_p is copied out
+    (copy_windows), scored by the neg_cent kernel and searched; with
+    ``scores`` a second sweep scores every panel again (the same kernel, the
+    same bits) and gathers the path's entries.  Memory: one panel of scores
+    and the decision words (Tt * Ts / 8 bytes).  No host sync: capture-safe."""
+    what = "maximum_path_durations_long"
+    require_device(z_p, m_p, logs_p, t_t, t_s)
+    z = z_p.detach().to(torch.float32).contiguous()
+    m = m_p.detach().to(torch.float32).contiguous()
+    lg = logs_p.detach().to(torch.float32).contiguous()
+    if z.dim() != 3 or m.shape != lg.shape or m.dim() != 3 or m.shape[:2] != z.shape[:2]:
+        raise _lib.VitsAmdError(f"{what}: z_p {tuple(z.shape)} m_p {tuple(m.shape)} "
+                                f"logs_p {tuple(lg.shape)}")
+    B, C, Tt = z.shape
+    Ts = m.shape[2]
+    if B > COPY_MAX_JOBS:
+        raise _lib.VitsAmdError(f"{what}: at most {COPY_MAX_JOBS} recordings a call")
+    job = _MasLongJob(what, B, Tt, Ts, t_t, t_s, strip, panel, scores, frame_token, z.device)
+    zpan = torch.empty(B * C * job.panel, device=z.device, dtype=torch.float32)
+    nc = torch.empty(B * job.panel * Ts, device=z.device, dtype=torch.float32)
+
+    def score(y0, rows):
+        # rows frames of every recording, contiguous [B][C][rows]
+        copy_windows(z, zpan, [(b * C * Tt + y0, b * C * rows, rows, rows) for b in range(B)],
+                     channels=C, src_rstride=Tt, dst_rstride=rows)
+        check(job.lib.vits_neg_cent(zpan.data_ptr(), m.data_ptr(), lg.data_ptr(), nc.data_ptr(),
+                                    B, C, rows, Ts, job.stream), "vits_neg_cent")
+
+    for y0, rows in job.panels():
+        score(y0, rows)
+        job.forward(nc.data_ptr(), rows * Ts, y0, rows)
+    job.backtrack()
+    if scores:
+        for y0, rows in job.panels():
+            score(y0, rows)
+            job.gather(nc.data_ptr(), rows * Ts, y0, rows)
+        job.sums()
+    return job.result()
+
+
 # ---------------------------------------------------------------------------
 # STFT magnitude with autograd
 # ---------------------------------------------------------------------------

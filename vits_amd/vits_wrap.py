@@ -366,6 +366,48 @@ class VITSWrap(object):
         return out
 
     @torch.no_grad()
+    def aligning_long(self, inputs: dict) -> dict:
+        """``aligning`` for a recording of any length whose text may split
+        into any number of segments: the request dict of ``aligning`` -> the
+        same dict plus flat "durations" (int32, the tokens of all segments in
+        order), "boundaries_s" (float64, one more entry than tokens),
+        "scores" (float32) and "frames" as there, "segtext" (a list, one per
+        segment) and "segments": a list of {"text", "start_s", "end_s",
+        "durations", "scores"}, one per segment, with the seconds of the
+        recording (at the model's rate) at which the segment starts and ends:
+        the points at which to cut it.  The segments share one emotion lookup,
+        as in ``speaking``.  Timing fields as in ``aligning``.  Needs a ROCm
+        GPU (EmoVITS.align_long)."""
+        utt_id = inputs.setdefault("id", str(time.time()).replace(".", "_"))
+        spkid = int(inputs.get("spkid", self.default_spkid))
+        ids, texts = self._split_utt_text(utt_id, inputs.get("text", "。"))
+        t0 = time.time()
+        parsed = [self.textparser(uid, text) for uid, text in zip(ids, texts)]
+        t1 = time.time()
+        sp = self.speecher
+        _, emotion = sp._resolve(spkid, inputs.get("emotion"))
+        durations, scores, seg_frames, frames = sp.align_long(
+            inputs["wav"], spkid, [vec for _, _, vec in parsed], [emotion] * len(parsed),
+            sampling_rate_in=inputs.get("sampling_rate_in"))
+        t_back = time.time() - t1
+        sec = sp.hop_size / sp.sampling_rate
+        out = inputs
+        out["durations"] = np.concatenate(durations)
+        out["boundaries_s"] = (np.concatenate([[0], np.cumsum(out["durations"], dtype=np.int64)])
+                               * sec)
+        out["scores"] = np.concatenate(scores)
+        out["frames"] = frames
+        out["segtext"] = [s.printer() if hasattr(s, "printer") else str(s) for _, s, _ in parsed]
+        out["segments"] = [
+            {"text": texts[i], "start_s": float(seg_frames[i] * sec),
+             "end_s": float(seg_frames[i + 1] * sec), "durations": durations[i],
+             "scores": scores[i]} for i in range(len(parsed))]
+        out["time_used_frontend"] = (t1 - t0) * 1000
+        out["time_used_backend"] = t_back * 1000
+        out["rtf"] = (t1 - t0 + t_back) / max(1e-9, frames * sec)
+        return out
+
+    @torch.no_grad()
     def speaking_many(self, list_of_inputs) -> list:
         """``speaking`` for several requests at once: one dict per input, the
         same ``wav``, ``sr`` and ``segment_info`` as ``[speaking(i) for i in
