@@ -1147,6 +1147,104 @@ int vits_copy_windows(const float* src, int64_t src_numel, int64_t src_rstride, 
                       int64_t dst_numel, int64_t dst_rstride, const vits_window_job* jobs,
                       int n_jobs, int channels, void* stream);
 
+/* ---------------------------------------------------------------------- */
+/* Speech editing: tokens [a, b_old) of a recording's text   */
+/* are replaced by tokens [a, b_new) of a new text; spans int32 [batch][3]  */
+/* = a | b_old | b_new.  All lengths are read on the device, no call keeps  */
+/* a host pointer, all three can be captured.  Durations are taken as       */
+/* min(max(d, 0), 2^18), the clamp of the _int entry points.                */
+/*                                                                          */
+/* vits_edit_pins (one 256-thread workgroup per row): from the recording's  */
+/* durations dur_old int32 [batch] rows of dur_old_bstride (token x <       */
+/* x_len_old[b]), cum = their prefix sums, f0 = cum[a), f1 = cum[b_old):    */
+/*   given[b][t] = dur_old[t]                 t < a                         */
+/*               = span_given[b][t] (NULL: -1)   a <= t < b_new             */
+/*               = dur_old[t - b_new + b_old]    b_new <= t < x_len_new[b]  */
+/*               = -1                            x_len_new[b] <= t < t_x_new*/
+/*   target[b]   = 0                           span_target NULL or [b] == 0 */
+/*               = y_len_old[b] - (f1 - f0) + span_target[b]      [b] > 0   */
+/*               = y_len_old[b]                 [b] < 0 (keep the length)   */
+/*   meta int32 [3][batch] = f0 | f1 | status                               */
+/* the inputs of vits_duration_plan over the new text.  status 1: a length  */
+/* outside [0, t_x], a span that is not 0 <= a <= b_old <= x_len_old, a <=  */
+/* b_new <= x_len_new with x_len_old - b_old == x_len_new - b_new, tokens   */
+/* whose durations are all 0 (no alignment), or sum(dur_old) != y_len_old:  */
+/* the row then gets given = 0 everywhere, target 0 and f0 = f1 = 0.        */
+/* VITS_E_ARG: a NULL pointer other than span_given / span_target, batch <= */
+/* 0, t_x <= 0; VITS_E_SHAPE: dur_old_bstride < t_x_old; VITS_E_UNSUP: a    */
+/* t_x > 4096.                                                              */
+/* ---------------------------------------------------------------------- */
+int vits_edit_pins(const int32_t* dur_old, int64_t dur_old_bstride, const int32_t* x_len_old,
+                   int t_x_old, const int32_t* x_len_new, int t_x_new, const int32_t* spans,
+                   const int32_t* span_given, const int32_t* span_target,
+                   const int32_t* y_len_old, int32_t* given, int32_t* target, int32_t* meta,
+                   int batch, void* stream);
+
+/* vits_edit_splice: the prior expansion of the new span and the splice in  */
+/* one pass.  dur_new int32 [batch] rows of dur_bstride (the plan's, token  */
+/* x < x_len_new[b], NULL: t_x), cum = their prefix sums, total = the last; */
+/* the pins make the prefix and the suffix of dur_new the old durations, so */
+/*   f0 = cum[a), n_new = cum[b_new) - f0, f1 = y_len_old - (total -        */
+/*   cum[b_new)), y_new = total = f0 + n_new + (y_len_old - f1)             */
+/*   z[b][c][t] = z_p_rec[b][c][t]                          t < f0          */
+/*              = m[b][c][x(t)] + noise[b][c][t] * s[b][c][x(t)]            */
+/*                                             f0 <= t < f0 + n_new         */
+/*              = z_p_rec[b][c][t - n_new + (f1 - f0)]                      */
+/*                                             f0 + n_new <= t < y_new      */
+/*              = 0                                     y_new <= t < t_y    */
+/* x(t) = the token with cum[x - 1] <= t < cum[x]; the product and the sum  */
+/* are two rounded fp32 operations, vits_expand_durations_int's expression  */
+/* at noise_scale 1.  m, s: [batch] of ms_bstride, channel rows of          */
+/* ms_cstride; noise [batch][channels][t_y] is indexed by output frame and  */
+/* read on the new span only; z_p_rec [batch][channels][t_rec] is read      */
+/* below y_len_old only.  Every element of z is written.  lens int32        */
+/* [n_stage][batch] = y_new * stage_mult[i]; meta int32 [4][batch] = f0 |   */
+/* n_new | f1 | status.  status -1: y_new > t_y (f0, n_new, f1 are still    */
+/* reported); status 1: not 0 <= a <= b_new <= x_len_new, b_old < a,        */
+/* y_len_old outside [0, t_rec] or f1 < f0 (f0 = n_new = f1 = 0); either    */
+/* way the row is zero and its lengths are 0.  Kept frames move as 16-byte  */
+/* vectors where source and destination are co-aligned (z and z_p_rec on a  */
+/* 16-byte boundary, t_y, t_rec and the suffix shift multiples of four; the */
+/* zero fill past y_new needs z and t_y alone), else one by one.            */
+/* VITS_E_ARG: a NULL pointer other than x_len_new, a z or z_p_rec off a    */
+/* 4-byte boundary, a size <= 0, n_stage outside [1, 8]; VITS_E_SHAPE:      */
+/* dur_bstride or ms_cstride < t_x, ms_bstride < 0, batch > 65535;          */
+/* VITS_E_UNSUP: t_x > 4096.                                                */
+int vits_edit_splice(const int32_t* dur_new, int64_t dur_bstride, const int32_t* x_len_new,
+                     int t_x, const int32_t* spans, const int32_t* y_len_old, const float* m,
+                     const float* s, int64_t ms_bstride, int32_t ms_cstride, const float* noise,
+                     const float* z_p_rec, int t_rec, float* z, int batch, int channels, int t_y,
+                     int32_t* lens, const int32_t* stage_mult, int n_stage, int32_t* meta,
+                     void* stream);
+
+/* vits_edit_patch: the waveform side.  orig [batch] rows of orig_bstride    */
+/* (orig_cap samples, the recording at the model rate), o likewise (the     */
+/* synthesis of the spliced latents), splice_meta = vits_edit_splice's      */
+/* meta.  With Ty = y_len_old[b], y_new = f0 + n_new + Ty - f1, L = y_new * */
+/* hop, margin in frames and fade in samples:                               */
+/*   lo = max(f0 - margin, 0) * hop, hi = min(f0 + n_new + margin, y_new) * */
+/*   hop, shift = (y_new - Ty) * hop;                                       */
+/*   fade > 0 and lo - fade < 0: lo = 0 and no fade in; fade > 0 and hi +   */
+/*   fade > L: hi = L and no fade out (the synthesis runs to that end);     */
+/*   out[i] = orig[i]                                      i < lo - fade    */
+/*          = orig[i] * (1 - w) + o[i] * w, w = (j + 0.5f) / fade,          */
+/*            j = i - (lo - fade)                    lo - fade <= i < lo    */
+/*          = o[i]                                         lo <= i < hi     */
+/*          = orig[i - shift] * (1 - w) + o[i] * w, w = (j + 0.5f) / fade,  */
+/*            j = hi + fade - 1 - i                  hi <= i < hi + fade    */
+/*          = orig[i - shift]                        hi + fade <= i < L     */
+/*          = 0                                      L <= i < out_cap       */
+/* j + 0.5f, the division, 1 - w, the two products and their sum are six    */
+/* separately rounded fp32 operations (no contraction).  out_len int32      */
+/* [batch] = L.  A row whose splice status is not 0, or whose Ty * hop >    */
+/* orig_cap or L > o_cap or L > out_cap, is zero with out_len 0.            */
+/* VITS_E_ARG: a NULL pointer, batch / cap / hop <= 0, margin or fade < 0;  */
+/* VITS_E_SHAPE: a row stride below its cap, batch > 65535.                 */
+int vits_edit_patch(const float* orig, int64_t orig_bstride, int orig_cap, const float* o,
+                    int64_t o_bstride, int o_cap, const int32_t* y_len_old,
+                    const int32_t* splice_meta, int hop, int margin, int fade, float* out,
+                    int64_t out_bstride, int out_cap, int32_t* out_len, int batch, void* stream);
+
 /* library introspection */
 const char* vits_amd_version(void);
 int vits_amd_device_arch(char* buf, int len);

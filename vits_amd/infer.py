@@ -1287,6 +1287,255 @@ class EmoVITS(object):
                                     sampling_rate_in, noise_scale)
         return out
 
+    # -- speech editing: a span of a recording re-spoken with new text
+    @staticmethod
+    def edit_span(text_old, text_new):
+        """The span (a, b_old, b_new) that turns text_old [N, c] into
+        text_new [M, c]: a = the longest common prefix of token rows, then the
+        longest common suffix of what remains, so that tokens [a, b_old) of
+        the old text are replaced by tokens [a, b_new) of the new one
+        (identical texts: (N, N, N), an empty edit at the end)."""
+        old, new = np.asarray(text_old), np.asarray(text_new)
+        n, m = old.shape[0], new.shape[0]
+        a = 0
+        while a < min(n, m) and np.array_equal(old[a], new[a]):
+            a += 1
+        k = 0
+        while k < min(n, m) - a and np.array_equal(old[n - 1 - k], new[m - 1 - k]):
+            k += 1
+        return a, n - k, m - k
+
+    def _edit_check(self, n_in, sampling_rate_in, text_old, text_new, span, durations,
+                    token_scale, span_frames, durations_old):
+        """Everything about an edit the host can refuse before anything is
+        uploaded (ValueError): returns (span, frames, given int32 [Tx_new] or
+        None, scale fp32 [Tx_new] or None, span_target, durations_old int32
+        [Tx_old] or None)."""
+        n_old, n_new = int(text_old.shape[0]), int(text_new.shape[0])
+        span = self.edit_span(text_old, text_new) if span is None else tuple(int(v) for v in span)
+        a, b_old, b_new = span if len(span) == 3 else (-1, -1, -1)
+        if not (0 <= a <= b_old <= n_old and a <= b_new <= n_new and n_old - b_old == n_new - b_new
+                and np.array_equal(text_old[:a], text_new[:a])
+                and np.array_equal(text_old[b_old:], text_new[b_new:])):
+            raise ValueError(f"span {span} does not turn the old text ({n_old} tokens) into the "
+                             f"new one ({n_new} tokens)")
+        frames = self._vc_plan(n_in, sampling_rate_in)[2]  # (over VC_MAX_FRAMES: ValueError)
+        if n_old < 1 or frames < n_old:
+            raise ValueError(f"recording of {frames} frames cannot be aligned with {n_old} "
+                             "tokens: every token takes at least one frame")
+        if max(n_old, n_new) > self.ALIGN_MAX_TOKENS:
+            raise ValueError(f"text of {max(n_old, n_new)} tokens exceeds the alignment kernel's "
+                             f"{self.ALIGN_MAX_TOKENS}")
+        target = 0
+        if span_frames is not None:
+            if b_new == a:
+                raise ValueError("span_frames needs a new span: this edit only deletes")
+            if isinstance(span_frames, str) and span_frames == "keep":
+                target = -1
+            elif isinstance(span_frames, (int, np.integer)) and span_frames > 0:
+                target = int(span_frames)
+            else:
+                raise ValueError(f"span_frames must be None, an int > 0 or 'keep', got "
+                                 f"{span_frames!r}")
+        given = None
+        if durations is not None:
+            d = np.asarray(durations).reshape(-1)
+            given = np.full(n_new, -1, np.int32)
+            if d.shape[0] == n_new:
+                given[a:b_new] = d[a:b_new]
+            elif d.shape[0] == b_new - a:
+                given[a:b_new] = d
+            else:
+                raise ValueError(f"durations need {n_new} values (or {b_new - a} for the span), "
+                                 f"got {d.shape[0]}")
+        scale = None
+        if token_scale is not None:
+            scale = np.asarray(token_scale, np.float32).reshape(-1)
+            if scale.shape[0] != n_new or not bool(np.all(scale >= 0)):
+                raise ValueError(f"token_scale needs {n_new} factors >= 0")
+        if durations_old is not None:
+            durations_old = np.asarray(durations_old).reshape(-1).astype(np.int32)
+            if (durations_old.shape[0] != n_old or bool((durations_old < 0).any())
+                    or int(durations_old.sum()) != frames):
+                raise ValueError(f"durations_old must be {n_old} frame counts >= 0 that sum to "
+                                 f"the recording's {frames} frames")
+        return span, frames, given, scale, target, durations_old
+
+    def _edit_rows(self, wav, spkid, text_old, text_new, emo, span, sampling_rate_in, durations,
+                   token_scale, span_frames, duration_rate, noise_scale, durations_old, emo_new,
+                   patch, margin_frames, fade, post=None):
+        """One edit through one graph, cached in self._graphs under ("edit",
+        old text bucket, new text bucket, recording frame bucket, output frame
+        bucket, durations_old given) (graph=False: the same edit_bucketed
+        call, eagerly, on the same padded inputs).  Returns (wav_out [1, n]
+        fp32 on the device, or ``post(wav_out, lengths, length_scale)``'s
+        result; y_new; dur_new; (f0, n_new, f1); scores) after ONE small
+        device-to-host copy (meta, durations and scores)."""
+        stft = self._vc_begin("edit")
+        hop = self.hop_size
+        text_old = np.ascontiguousarray(text_old)
+        text_new = np.ascontiguousarray(text_new)
+        n_in = np.asarray(wav).reshape(-1).shape[0]
+        span, frames, given, scale, target, durations_old = self._edit_check(
+            n_in, sampling_rate_in, text_old, text_new, span, durations, token_scale, span_frames,
+            durations_old)
+        n_old, n_new = text_old.shape[0], text_new.shape[0]
+        margin = self.model.edit_context_frames() if margin_frames is None else int(margin_frames)
+        fade = hop if fade is None else int(fade)
+        if margin < 0 or fade < 0:
+            raise ValueError("margin_frames and fade must be >= 0")
+        x, lens, _, trb, _, _ = self._vc_upload([wav], sampling_rate_in, 0.0)
+        spk, e_old = self._resolve(spkid, emo)
+        e_new = e_old if emo_new is None else self._resolve(spkid, emo_new)[1]
+        xb_old, xb_new = self._text_bucket(n_old), self._text_bucket(n_new)
+        dev, dt, i32 = self.device, self.dtype, torch.int32
+        C = self.inter_channels
+        g_row = np.full(xb_new, -1, np.int32)
+        if given is not None:
+            g_row[:n_new] = given
+        s_row = np.ones(xb_new, np.float32)
+        if scale is not None:
+            s_row[:n_new] = scale
+        pad = self._pad_rows
+        inputs = dict(
+            wav=pad(x, 1, trb * hop + hop - 1), n=pad(lens, 1, dtype=i32),
+            x_old=pad(self._text_rows([text_old], [n_old]), 1, xb_old),
+            xl_old=pad([n_old], 1, dtype=i32),
+            x_new=pad(self._text_rows([text_new], [n_new]), 1, xb_new),
+            xl_new=pad([n_new], 1, dtype=i32), emo=e_old, emo_new=e_new,
+            sid=pad([int(spk)], 1, dtype=torch.long),
+            spans=torch.tensor([list(span)], dtype=i32).to(dev),
+            given=torch.from_numpy(g_row).view(1, -1).to(dev),
+            tok_scale=torch.from_numpy(s_row).view(1, -1).to(dev),
+            span_target=pad([target], 1, dtype=i32),
+            rate=torch.full((1,), float(duration_rate), device=dev),
+            noise_q=torch.zeros(1, C, trb, device=dev))
+        if durations_old is not None:
+            d_row = np.zeros(xb_old, np.int32)
+            d_row[:n_old] = durations_old
+            inputs["dur_old"] = torch.from_numpy(d_row).view(1, -1).to(dev)
+        y_len_old = pad([frames], 1, dtype=i32)
+        if self._vc_gen is None:
+            self._vc_gen = torch.Generator(device=dev)
+        gen_state = self._vc_gen.get_state()
+        memo = ("edit", xb_old, xb_new, trb)
+        while True:
+            tyb = trb if target < 0 else max(trb, self._ty_bucket.get(memo, trb))
+            # the prior noise of the whole output bucket, from the device
+            # generator of the conversion paths (a re-run draws from the same state)
+            self._vc_gen.set_state(gen_state)
+            if noise_scale > 0:
+                inputs["noise"] = torch.randn(1, C, tyb, device=dev,
+                                              generator=self._vc_gen) * float(noise_scale)
+            else:
+                inputs["noise"] = torch.zeros(1, C, tyb, device=dev)
+            if self.graph:
+                run = self._cached_graph(
+                    ("edit", 1, xb_old, xb_new, trb, tyb, durations_old is not None),
+                    lambda: self.model.capture_edit_bucketed(
+                        xb_old, xb_new, trb, tyb, stft=stft,
+                        given_durations=durations_old is not None))
+                for k, v in inputs.items():
+                    run.static[k].copy_(v)
+                o, lengths, dur_new, meta, scores = run.replay()
+            else:
+                i = inputs
+                o, lengths, dur_new, meta, scores = self.model.edit_bucketed(
+                    i["wav"], i["n"], i["x_old"], i["xl_old"], i["x_new"], i["xl_new"], i["emo"],
+                    i["emo_new"], i["sid"], i["spans"],
+                    {k: i[k] for k in ("given", "tok_scale", "span_target", "rate")},
+                    (i["noise"], i["noise_q"]), trb, tyb, stft=stft,
+                    durations_old=i.get("dur_old"))
+            w, scale_l = o[:, 0], hop  # (lengths: y_new in frames)
+            if patch:
+                w, lengths = ops.edit_patch(inputs["wav"], o[:, 0], y_len_old, meta[:4], hop,
+                                            margin=margin, fade=fade)
+                scale_l = 1
+            posted = None if post is None else post(w, lengths, scale_l)
+            parts = [meta[:, 0], dur_new[0, :n_new]]
+            if scores is not None:
+                parts.append(scores[0, :n_old].view(i32))
+            host = self._to_host(torch.cat(parts))  # the one copy back (synchronises)
+            f0, n_span, f1, s_st, p_st, d_st = (int(v) for v in host[:6])
+            if p_st:
+                raise ValueError("the old durations do not describe the recording (no alignment, "
+                                 f"or their sum is not its {frames} frames)")
+            if d_st:
+                raise ValueError(f"span_frames={span_frames!r} cannot be met: the span's pins "
+                                 "leave no room for it")
+            if s_st == 1:
+                raise ValueError(f"span {span} cannot be spliced into this recording")
+            y_new = f0 + n_span + frames - f1
+            if s_st == -1:
+                if y_new > self.VC_MAX_FRAMES:
+                    raise ValueError(f"edited recording of {y_new} frames exceeds the largest "
+                                     f"bucket of {self.VC_MAX_FRAMES} frames")
+                # re-run at the next output bucket, which this memo keeps.  (The
+                # patch and the post stage of this attempt ran over a zero row: the
+                # status is known only after the copy.  _grow_bucket puts numpy's
+                # generator back for the synthesis paths; this one never draws from
+                # it, so it is handed the state as it is.)
+                self._grow_bucket(memo, np.random.get_state(), tyb, y_new)
+                continue
+            dur = host[6:6 + n_new].copy()
+            sc = host[6 + n_new:].view(np.float32).copy() if scores is not None else None
+            return (w if post is None else posted), y_new, dur, (f0, n_span, f1), sc
+
+    def edit(self, wav, spkid, text_old, text_new, emo, *, span=None, sampling_rate_in=None,
+             durations=None, token_scale=None, span_frames=None, duration_rate=1.0,
+             noise_scale=0.667, durations_old=None, emo_new=None, patch=False, margin_frames=None,
+             fade=None):
+        """Re-speak part of a recording: ``wav`` (as ``convert`` takes it) is
+        speaker spkid saying text_old [N, c]; the result says text_new [M, c].
+        ``span`` = (a, b_old, b_new) (default: edit_span of the two texts):
+        tokens [a, b_old) of the old text become tokens [a, b_new) of the new
+        one.  The recording is aligned with its text (or ``durations_old``
+        taken as its alignment), the new text is encoded as a whole, the new
+        span gets durations from the duration plan (``durations``: frames for
+        the span's tokens, < 0 free; ``token_scale``; ``duration_rate``;
+        ``span_frames``: an int, the new span lasts exactly that many frames,
+        or "keep", it lasts what the old one did) and its prior (noise from
+        this object's device generator times ``noise_scale``) is spliced
+        between the recording's own latents, which the reverse flow and the
+        decoder then render as one utterance: SynthesizerTrn.edit, through one
+        cached graph and one small device-to-host copy.  ``patch``: outside
+        the edited frames widened by ``margin_frames`` (default
+        edit_context_frames()) the samples are the recording's own, with a
+        cross-fade of ``fade`` samples (default one hop) at each seam
+        (ops.edit_patch); else the whole result is the model's rendering.
+
+        Returns (wav float32 [y_new * hop] at the model's rate, dur_new int32
+        [M], (f0, n_new, f1) the edited frames [f0, f1) of the recording and
+        [f0, f0 + n_new) of the result, scores float32 [N] of the alignment or
+        None with durations_old).  Raises ValueError, before anything is
+        uploaded, for a span that does not match the texts, a recording of
+        more than 4096 frames or of fewer frames than tokens, span_frames with
+        an empty new span; after the copy for durations that do not describe
+        the recording or a span_frames that cannot be met."""
+        w, y_new, dur, pos, scores = self._edit_rows(
+            wav, spkid, text_old, text_new, emo, span, sampling_rate_in, durations, token_scale,
+            span_frames, duration_rate, noise_scale, durations_old, emo_new, patch, margin_frames,
+            fade)
+        return w[0, :y_new * self.hop_size].cpu().numpy(), dur, pos, scores
+
+    def edit_pcm(self, wav, spkid, text_old, text_new, emo, *, span=None, sampling_rate_in=None,
+                 durations=None, token_scale=None, span_frames=None, duration_rate=1.0,
+                 noise_scale=0.667, durations_old=None, emo_new=None, patch=True,
+                 margin_frames=None, fade=None, pitch=1.0, sampling_rate=None, volume=1.0,
+                 tail_silence=0.0):
+        """edit plus convert_pcm's output stage on the device (pitch /
+        sampling-rate resampling, volume, clip, int16, tail silence), the
+        length read on the device; ``patch`` defaults to True.  Returns (pcm
+        int16 [n], n_model_samples, dur_new, (f0, n_new, f1), scores)."""
+        out = self._output(pitch, sampling_rate, volume, tail_silence)
+        pcm, y_new, dur, pos, scores = self._edit_rows(
+            wav, spkid, text_old, text_new, emo, span, sampling_rate_in, durations, token_scale,
+            span_frames, duration_rate, noise_scale, durations_old, emo_new, patch, margin_frames,
+            fade, post=lambda w, lengths, scale: self._post(w, out, lengths=lengths,
+                                                            length_scale=scale))
+        n = y_new * self.hop_size
+        return pcm[0, :self._n_out(n, out.passes) + out.tail].cpu().numpy(), n, dur, pos, scores
+
     # -- forced alignment of long recordings: many segments, any length (DESIGN.md 4u)
     # the caps of align_long: the total tokens of a text (a 40-minute reading
     # at 1 token per 6 frames), and the bytes of the search's workspace plus

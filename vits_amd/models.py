@@ -1310,6 +1310,342 @@ class SynthesizerTrn(nn.Module):
 
         return self._graph_run(run, graph, static, t_x=t_x, t_y=t_y, batch=batch)
 
+    # ---------------------------------------------------------- speech editing
+    def edit_context_frames(self):
+        """Frames on each side of an edited span whose samples the edit can
+        change: further from the span than this, ``edit`` returns the plain
+        reconstruction of the recording.  Between the spliced z_p and the
+        samples lie the reverse flow (every coupling's WN stack, once) and the
+        decoder (Generator.context_frames); enc_q and the forward flow ran on
+        the untouched recording."""
+        def wn(m):
+            k = m.kernel_size[0]
+            return sum((k - 1) // 2 * m.dilation_rate ** i for i in range(m.n_layers))
+
+        flow = sum(wn(f.enc) for f in self.flow.flows
+                   if isinstance(f, modules.ResidualCouplingLayer))
+        return flow + self.dec.context_frames()
+
+    def _edit_tail(self, dur_new, spans, y_len, x_len_new, m_p, s_p, g, noise, z_p_rec, keep=False):
+        """The acoustic side of an edit: splice, reverse flow, decoder, cut at
+        y_new * hop; kernels only, no host sync.  Returns (o fp32 [B, 1, t_y *
+        hop], lens, splice meta, (z_p, z_hat) when ``keep`` else None)."""
+        z, lens, smeta = engine.ops.edit_splice(dur_new, spans, y_len, m_p, s_p, noise, z_p_rec,
+                                                x_len=x_len_new, stage_mult=self._stage_mult())
+        z_p = z.clone() if keep else None
+        gf = engine._f32(g)
+        engine.get_plan(self.flow, engine.CouplingFlowPlan).run_(z, gf, lengths=lens[0])
+        o = engine.get_plan(self.dec, engine.GeneratorPlan).run(z, gf, lengths=lens[1:])
+        out = torch.empty_like(o)  # (the cut of _vc_core)
+        engine.ops.resample_poly(o[:, 0], 1, 1, lengths=lens[0], length_scale=self.hop_total,
+                                 out=out[:, 0])
+        return out, lens, smeta, ((z_p, z) if keep else None)
+
+    @staticmethod
+    def _span_target(span_frames, dev):
+        """span_frames (None, an int > 0 or "keep") as vits_edit_pins' span_target."""
+        if span_frames is None:
+            return None
+        if isinstance(span_frames, str) and span_frames == "keep":
+            v = -1
+        elif hasattr(span_frames, "__index__") and not isinstance(span_frames, bool) \
+                and int(span_frames) > 0:
+            v = int(span_frames)
+        else:
+            raise ValueError(f"edit: span_frames must be None, an int > 0 or 'keep', got "
+                             f"{span_frames!r}")
+        return torch.full((1,), v, device=dev, dtype=torch.int32)
+
+    @torch.no_grad()
+    def edit(self, y, y_lengths, x_old, x_new, emo, sid, span, *, durations_old=None, given=None,
+             tok_scale=None, span_frames=None, length_scale=1.0, noise=None, noise_q=None,
+             emo_new=None):
+        """Re-speak a span of a recording with new text, in latent space.  y
+        [1, F, Ty] is the linear spectrogram of speaker sid saying x_old [1,
+        Tx_old, c]; ``span`` = (a, b_old, b_new): tokens [a, b_old) of x_old
+        are replaced by tokens [a, b_new) of x_new [1, Tx_new, c] (the texts
+        agree on the first a tokens and on the last Tx_old - b_old == Tx_new -
+        b_new; b_old == a inserts, b_new == a deletes).  Eager, B = 1, exact
+        lengths: the definition edit_bucketed is held to.
+
+        dur_old = ``durations_old`` (Tx_old ints) or align(x_old, ..., y,
+        ...)[0]; f0 = sum(dur_old[:a]), f1 = sum(dur_old[:b_old]).  m_p, s_p,
+        logw, g come from the text side of x_new (``emo_new`` or ``emo``).
+        The new text's durations are ops.duration_plan's under the pins
+        dur_old outside the span and ``given`` inside it (Tx_new ints, or
+        b_new - a ints for the span alone; default -1 = free), ``tok_scale``,
+        ``length_scale`` as its rate and the row target ``span_frames``: None,
+        an int (the new span lasts exactly that many frames) or "keep" (the
+        span keeps its old length).  z_p_rec = flow(enc_q(y); g) is
+        _audio_latents' (``noise_q`` [1, C, Ty] pre-scaled, None: the
+        posterior mean).  With n_new = sum(dur_new[a:b_new]) and y_new = f0 +
+        n_new + Ty - f1, the spliced z_p is z_p_rec[:, :f0], then m_p[:, x(t)]
+        + noise[:, t] * s_p[:, x(t)] on the new span (``noise`` [1, C, y_new]
+        pre-scaled, indexed by output frame; None: zeros), then z_p_rec[:,
+        f1:Ty] (ops.edit_splice); o = dec(flow^-1(z_p; g); g) masked at y_new.
+
+        Returns (o [1, 1, y_new * hop] in y's dtype, as voice_conversion
+        returns it, dur_new int32 [Tx_new], (f0, n_new, f1), scores fp32
+        [Tx_old] or None with durations_old, (z_p, z_hat)).
+        Samples further than edit_context_frames() frames from the new span
+        are bit for bit voice_conversion(y, ., sid, sid)."""
+        engine._check_gpu(y, "SynthesizerTrn.edit")
+        if y.size(0) != 1 or x_old.size(0) != 1 or x_new.size(0) != 1:
+            raise ValueError("edit: one recording per call (edit_bucketed takes batches)")
+        dev, dt = y.device, x_new.dtype
+        i32 = torch.int32
+        Ty, Tx_old, Tx_new = int(y_lengths.reshape(-1)[0]), x_old.size(1), x_new.size(1)
+        a, b_old, b_new = (int(v) for v in span)
+        if not (0 <= a <= b_old <= Tx_old and a <= b_new <= Tx_new
+                and Tx_old - b_old == Tx_new - b_new):
+            raise ValueError(f"edit: span {(a, b_old, b_new)} does not fit texts of {Tx_old} and "
+                             f"{Tx_new} tokens")
+        y_len = torch.full((1,), Ty, device=dev, dtype=i32)
+        xl_old = torch.full((1,), Tx_old, device=dev, dtype=i32)
+        xl_new = torch.full((1,), Tx_new, device=dev, dtype=i32)
+        spans = torch.tensor([[a, b_old, b_new]], dtype=i32).to(dev)
+        spec = engine._f32(y)[:, :, :Ty].contiguous()
+        g = self.emb_g(sid)
+        scores = None
+        if durations_old is None:
+            dur_old, scores, (z_p_rec, _, _, _) = self._align_core(spec, noise_q, y_len, x_old,
+                                                                   xl_old, emo, sid)
+        else:
+            dur_old = torch.as_tensor(durations_old).reshape(1, -1).to(device=dev, dtype=i32)
+            if dur_old.shape[1] != Tx_old:
+                raise ValueError(f"edit: {Tx_old} old tokens need {Tx_old} durations_old, got "
+                                 f"{dur_old.shape[1]}")
+            _, z_p_rec, _ = self._audio_latents(spec, noise_q, y_len, engine._f32(g))
+        span_given = None
+        if given is not None:
+            gv = torch.as_tensor(given).reshape(-1).to(i32)
+            span_given = torch.full((1, Tx_new), -1, dtype=i32)
+            if gv.numel() == Tx_new:
+                span_given[0] = gv
+            elif gv.numel() == b_new - a:
+                span_given[0, a:b_new] = gv
+            else:
+                raise ValueError(f"edit: given needs {Tx_new} values (or {b_new - a} for the "
+                                 f"span), got {gv.numel()}")
+            span_given = span_given.to(dev)
+        if tok_scale is not None:
+            tok_scale = torch.as_tensor(tok_scale, dtype=torch.float32).reshape(1, Tx_new).to(
+                dev).contiguous()
+        pins, target, pmeta = engine.ops.edit_pins(
+            dur_old.contiguous(), xl_old, xl_new, Tx_new, spans, y_len, span_given=span_given,
+            span_target=self._span_target(span_frames, dev))
+        m_p, s_p, logw, _ = self.infer_p1(x_new, emo if emo_new is None else emo_new, sid)
+        dur_new, total, pstat = engine.ops.duration_plan(
+            logw, rate=float(length_scale), half_round=dt == torch.float16, given=pins,
+            tok_scale=tok_scale, target=target)
+        # exact lengths: the one host visit of the eager definition
+        pm, y_new, ps = pmeta.cpu(), int(total.item()), int(pstat.item())
+        if int(pm[2, 0]) != 0:
+            raise ValueError("edit: the old durations do not describe the recording (no "
+                             f"alignment, or their sum is not its {Ty} frames)")
+        if ps != 0:
+            raise ValueError(f"edit: span_frames={span_frames!r} cannot be met by the new span")
+        C = self.inter_channels
+        if noise is None:
+            noise = torch.zeros(1, C, max(y_new, 1), device=dev)
+        noise = engine._f32(noise).contiguous()
+        if tuple(noise.shape) != (1, C, max(y_new, 1)):
+            raise ValueError(f"edit: the edited recording has {y_new} frames: noise must be "
+                             f"[1, {C}, {max(y_new, 1)}], got {tuple(noise.shape)}")
+        o, _, smeta, zs = self._edit_tail(dur_new, spans, y_len, xl_new, m_p, s_p, g, noise,
+                                          z_p_rec.contiguous(), keep=True)
+        f0, n_new, f1, st = (int(v) for v in smeta.cpu()[:, 0])
+        if st != 0:
+            raise ValueError(f"edit: the splice refused the row (status {st})")
+        return (o[:, :, :y_new * self.hop_total].to(y.dtype), dur_new[0], (f0, n_new, f1),
+                None if scores is None else scores[0], tuple(t.to(y.dtype) for t in zs))
+
+    @torch.no_grad()
+    def edit_bucketed(self, wav, n_samples, x_old, x_old_len, x_new, x_new_len, emo, emo_new, sid,
+                      spans, controls, noise, t_rec, t_y, *, stft, durations_old=None):
+        """``edit`` from the waveform with NO host synchronisation, over
+        static buckets of t_rec recording frames and t_y output frames
+        (capture_edit_bucketed makes it one hipGraph).  wav [B, >= t_rec *
+        hop] fp32 and n_samples int32 [B] as convert_bucketed takes them
+        (``stft`` too); x_old [B, t_x_old, c] / x_new [B, t_x_new, c] with
+        x_old_len / x_new_len int32 [B] on the device; emo / emo_new [B, 1024]
+        (emo_new None: emo); spans int32 [B, 3]; ``controls`` = None or
+        dict(given= int32 [B, t_x_new], tok_scale= fp32 [B, t_x_new],
+        span_target= int32 [B] (> 0 exact frames of the new span, 0 none, < 0
+        keep), rate= a number or fp32 [B]); ``noise`` = the prior noise [B, C,
+        t_y] (pre-scaled, indexed by output frame) or a pair (noise, noise_q
+        [B, C, t_rec]); ``durations_old`` int32 [B, t_x_old]: the alignment is
+        skipped (x_old and emo are then not read).
+
+        The chain: ragged STFT -> _audio_latents -> old text -> neg_cent ->
+        MAS durations -> edit_pins -> new text + duration predictor ->
+        duration_plan -> edit_splice -> reverse flow -> decoder -> cut, under
+        ops.length_skip(64).  Returns (o fp32 [B, 1, t_y * hop], y_new int32
+        [B], dur_new int32 [B, t_x_new], meta int32 [6, B] = f0 | n_new | f1 |
+        splice status | pins status | plan status, scores fp32 [B, t_x_old] or
+        None): where all three statuses are 0, the first y_new * hop samples
+        of row b are bit for bit ``edit`` of that row alone; a row whose
+        splice status is not 0 is zero with y_new 0."""
+        engine._check_gpu(wav, "SynthesizerTrn.edit_bucketed")
+        t_rec, t_y = int(t_rec), int(t_y)
+        dev, dt = wav.device, x_new.dtype
+        B = wav.shape[0]
+        noise, noise_q = noise if isinstance(noise, (tuple, list)) else (noise, None)
+        controls = dict(controls or {})
+        unknown = set(controls) - {"given", "tok_scale", "span_target", "rate"}
+        if unknown:
+            raise ValueError(f"edit_bucketed: unknown control(s) {sorted(unknown)}")
+        if x_new.dim() != 3 or x_new.shape[0] != B or tuple(noise.shape) != (
+                B, self.inter_channels, t_y):
+            raise ValueError(f"edit_bucketed: x_new must be [{B}, t_x_new, c] and noise [{B}, "
+                             f"{self.inter_channels}, {t_y}]")
+        spec, y_len = self._spec_rows("edit_bucketed", wav, n_samples, t_rec, stft)
+        xl_old = x_old_len.to(device=dev, dtype=torch.int32).contiguous()
+        xl_new = x_new_len.to(device=dev, dtype=torch.int32).contiguous()
+        g = self.emb_g(sid)
+        scores = None
+        with engine.ops.length_skip(64):
+            if durations_old is None:
+                dur_old, scores, (z_p_rec, _, _, _) = self._align_core(spec, noise_q, y_len, x_old,
+                                                                       xl_old, emo, sid)
+            else:
+                dur_old = durations_old
+                _, z_p_rec, _ = self._audio_latents(spec, noise_q, y_len, engine._f32(g))
+            pins, target, pmeta = engine.ops.edit_pins(
+                dur_old, xl_old, xl_new, x_new.shape[1], spans, y_len,
+                span_given=controls.get("given"), span_target=controls.get("span_target"))
+            h, m_p, s_p = self.enc_p.forward_masked_hip(
+                x_new, xl_new, emo if emo_new is None else emo_new, g, exp_logs=True,
+                pad_exact=True)
+            logw = engine.get_plan(self.dp, engine.DurationPlan).run(h, g, lengths=xl_new)
+            m_p, s_p, logw = m_p.to(dt), s_p.to(dt), logw.to(dt)
+            dur_new, _, pstat = engine.ops.duration_plan(
+                logw, rate=controls.get("rate", 1.0), x_len=xl_new,
+                half_round=dt == torch.float16, given=pins, tok_scale=controls.get("tok_scale"),
+                target=target)
+            o, lens, smeta, _ = self._edit_tail(dur_new, spans, y_len, xl_new, m_p, s_p, g, noise,
+                                                z_p_rec)
+        meta = torch.cat([smeta, pmeta[2:3], pstat.reshape(1, B)], dim=0)
+        return o, lens[0], dur_new, meta, scores
+
+    @torch.no_grad()
+    def capture_edit_bucketed(self, t_x_old, t_x_new, t_rec, t_y, batch=1, warmup=2, *, stft,
+                              given_durations=False):
+        """One hipGraph for edit_bucketed over [batch, t_x_old / t_x_new
+        tokens, t_rec recording frames, t_y output frames] (``stft`` as
+        there; ``given_durations``: the graph reads durations_old from a
+        static buffer and holds no alignment).  Returns run(wav, n_samples,
+        x_old, x_old_len, x_new, x_new_len, emo, emo_new, sid, spans,
+        controls=None, noise=None, noise_q=None, durations_old=None) ->
+        edit_bucketed's outputs as views of static buffers.  wav [n, <= t_rec
+        * hop + hop - 1] fp32 rows, x_old [n, <= t_x_old, c] (None with
+        given_durations), x_new [n, <= t_x_new, c], emo / emo_new [n, 1024]
+        (emo_new None: emo), the lengths, sid and spans host ints (or
+        tensors), ``controls`` a list of n dicts(given=, tok_scale=,
+        span_target=, rate=) or None, noise [n, C, t_y] / noise_q [n, C,
+        t_rec] (None: the static buffer is zeroed), durations_old [n, <=
+        t_x_old] ints.  Rows at or past n get zero text and length 0: they
+        come back with pins status 1.  ``run.replay()`` replays for a caller
+        who has filled ``run.static`` itself."""
+        dev = next(self.parameters()).device
+        dt = next(self.parameters()).dtype
+        n_fft, hop, win = (int(v) for v in stft)
+        t_x_old, t_x_new, t_rec, t_y, batch = (int(v) for v in (t_x_old, t_x_new, t_rec, t_y,
+                                                                 batch))
+        C = self.inter_channels
+        cap = t_rec * hop + hop - 1
+        i32 = torch.int32
+        static = dict(wav=torch.zeros(batch, cap, device=dev),
+                      n=torch.zeros(batch, device=dev, dtype=i32),
+                      x_old=torch.zeros(batch, t_x_old, self.text_channels, device=dev, dtype=dt),
+                      xl_old=torch.zeros(batch, device=dev, dtype=i32),
+                      x_new=torch.zeros(batch, t_x_new, self.text_channels, device=dev, dtype=dt),
+                      xl_new=torch.zeros(batch, device=dev, dtype=i32),
+                      emo=torch.zeros(batch, 1024, device=dev, dtype=dt),
+                      emo_new=torch.zeros(batch, 1024, device=dev, dtype=dt),
+                      sid=torch.zeros(batch, device=dev, dtype=torch.long),
+                      spans=torch.zeros(batch, 3, device=dev, dtype=i32),
+                      given=torch.full((batch, t_x_new), -1, device=dev, dtype=i32),
+                      tok_scale=torch.ones(batch, t_x_new, device=dev),
+                      span_target=torch.zeros(batch, device=dev, dtype=i32),
+                      rate=torch.ones(batch, device=dev),
+                      noise=torch.zeros(batch, C, t_y, device=dev),
+                      noise_q=torch.zeros(batch, C, t_rec, device=dev))
+        if given_durations:
+            static["dur_old"] = torch.zeros(batch, t_x_old, device=dev, dtype=i32)
+        self._vc_window(win, dev)  # (built outside the capture)
+        ctl = {k: static[k] for k in ("given", "tok_scale", "span_target", "rate")}
+
+        def body():
+            return self.edit_bucketed(
+                static["wav"], static["n"], static["x_old"], static["xl_old"], static["x_new"],
+                static["xl_new"], static["emo"], static["emo_new"], static["sid"], static["spans"],
+                ctl, (static["noise"], static["noise_q"]), t_rec, t_y, stft=(n_fft, hop, win),
+                durations_old=static.get("dur_old"))
+
+        graph, out = self._capture_body(body, warmup, dev)
+        _ints = self._row_ints
+
+        def replay():
+            graph.replay()
+            return out
+
+        def run(wav, n_samples, x_old, x_old_len, x_new, x_new_len, emo, emo_new, sid, spans,
+                controls=None, noise=None, noise_q=None, durations_old=None):
+            n = wav.shape[0]
+            if not 1 <= n <= batch or wav.shape[1] > cap:
+                raise ValueError(f"edit replay: wav {tuple(wav.shape)} does not fit "
+                                 f"[{batch}, {cap}]")
+            if x_new.shape[0] != n or x_new.shape[1] > t_x_new or (
+                    x_old is not None and (x_old.shape[0] != n or x_old.shape[1] > t_x_old)):
+                raise ValueError(f"edit replay: the texts do not fit [{n}, {t_x_old} / {t_x_new}, c]")
+            if given_durations != (durations_old is not None):
+                raise ValueError("edit replay: durations_old go with a graph captured with "
+                                 "given_durations, and only with it")
+            static["wav"].zero_()
+            static["wav"][:n, :wav.shape[1]].copy_(wav)
+            _fill_rows(static["n"], _ints(n_samples, n, i32), n)
+            if x_old is not None:
+                _fill_rows(static["x_old"], x_old, n, x_old.shape[1])
+            _fill_rows(static["xl_old"], _ints(x_old_len, n, i32), n)
+            _fill_rows(static["x_new"], x_new, n, x_new.shape[1])
+            _fill_rows(static["xl_new"], _ints(x_new_len, n, i32), n)
+            _fill_rows(static["emo"], emo, n)
+            _fill_rows(static["emo_new"], emo if emo_new is None else emo_new, n)
+            _fill_rows(static["sid"], _ints(sid, n, torch.long), n)
+            _fill_rows(static["spans"], torch.as_tensor(spans, dtype=i32).reshape(n, 3), n)
+            given = torch.full((batch, t_x_new), -1, dtype=i32)
+            scale = torch.ones(batch, t_x_new)
+            target = torch.zeros(batch, dtype=i32)
+            rate = torch.ones(batch)
+            for i, row in enumerate(controls or ()):
+                row = row or {}
+                unknown = set(row) - set(ctl)
+                if unknown or i >= n:
+                    raise ValueError(f"edit replay: controls {sorted(unknown)} of row {i}")
+                for buf, v in ((given, row.get("given")), (scale, row.get("tok_scale"))):
+                    if v is not None:
+                        v = torch.as_tensor(v, dtype=buf.dtype).reshape(-1)
+                        buf[i, :v.numel()] = v
+                if row.get("span_target") is not None:
+                    target[i] = int(row["span_target"])
+                if row.get("rate") is not None:
+                    rate[i] = float(row["rate"])
+            for k, v in (("given", given), ("tok_scale", scale), ("span_target", target),
+                         ("rate", rate)):
+                static[k].copy_(v)
+            for k, v in (("noise", noise), ("noise_q", noise_q)):
+                static[k].zero_()
+                if v is not None:
+                    static[k][:n].copy_(v)
+            if given_durations:
+                d = torch.as_tensor(durations_old, dtype=i32).reshape(n, -1)
+                _fill_rows(static["dur_old"], d, n, d.shape[1])
+            return replay()
+
+        return self._graph_run(run, graph, static, t_x_old=t_x_old, t_x_new=t_x_new, t_rec=t_rec,
+                               t_y=t_y, batch=batch, replay=replay)
+
     # --------------------------------------- the two halves, captured apart
     @torch.no_grad()
     def capture_infer_p1(self, t_x, warmup=2):

@@ -2254,3 +2254,141 @@ def copy_windows(src: torch.Tensor, dst: torch.Tensor, jobs, *, channels: int = 
             int(dst_rstride), table, len(part), int(channels), _stream_ptr(src.device)),
             "vits_copy_windows")
     return dst
+
+
+# ---------------------------------------------------------------------------
+# speech editing (edit.hip)
+# ---------------------------------------------------------------------------
+
+
+def _edit_arg(what: str, t, dtype, shape, name: str, optional: bool = False):
+    """A contiguous device tensor of exactly this dtype and shape (or None
+    where ``optional``)."""
+    if t is None and optional:
+        return None
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape)
+            or not t.is_contiguous()):
+        raise _lib.VitsAmdError(f"{what}: {name} must be a contiguous {dtype} {list(shape)} tensor")
+    require_device(t)
+    return t
+
+
+def edit_pins(dur_old: torch.Tensor, x_len_old: torch.Tensor, x_len_new: torch.Tensor,
+              t_x_new: int, spans: torch.Tensor, y_len_old: torch.Tensor, *,
+              span_given: Optional[torch.Tensor] = None,
+              span_target: Optional[torch.Tensor] = None):
+    """The inputs of ``duration_plan`` over the new text of an edit, on the
+    device (vits_edit_pins, include/vits_amd.h has the rule): ``dur_old``
+    int32 [B, t_x_old] (rows may be strided), ``x_len_old`` / ``x_len_new`` /
+    ``y_len_old`` int32 [B], ``spans`` int32 [B, 3] = a | b_old | b_new,
+    ``span_given`` int32 [B, t_x_new] (the caller's pins, read inside the span
+    only), ``span_target`` int32 [B] (> 0: the new span lasts exactly that
+    many frames, 0: free, < 0: the row keeps its length).  Returns (given
+    int32 [B, t_x_new], target int32 [B], meta int32 [3, B] = f0 | f1 |
+    status); a status-1 row has all-zero pins and target 0."""
+    what = "edit_pins"
+    if (not isinstance(dur_old, torch.Tensor) or dur_old.dim() != 2
+            or dur_old.dtype != torch.int32 or dur_old.stride(1) != 1
+            or dur_old.stride(0) < dur_old.shape[1]):
+        raise _lib.VitsAmdError(f"{what}: dur_old must be an int32 [B, t_x_old] tensor with "
+                                "contiguous rows")
+    require_device(dur_old)
+    B, t_x_old = dur_old.shape
+    t_x_new = int(t_x_new)
+    i32 = torch.int32
+    x_len_old = _edit_arg(what, x_len_old, i32, (B,), "x_len_old")
+    x_len_new = _edit_arg(what, x_len_new, i32, (B,), "x_len_new")
+    y_len_old = _edit_arg(what, y_len_old, i32, (B,), "y_len_old")
+    spans = _edit_arg(what, spans, i32, (B, 3), "spans")
+    span_given = _edit_arg(what, span_given, i32, (B, t_x_new), "span_given", True)
+    span_target = _edit_arg(what, span_target, i32, (B,), "span_target", True)
+    dev = dur_old.device
+    given = torch.empty(B, t_x_new, device=dev, dtype=i32)
+    target = torch.empty(B, device=dev, dtype=i32)
+    meta = torch.empty(3, B, device=dev, dtype=i32)
+    check(_lib.load().vits_edit_pins(
+        dur_old.data_ptr(), dur_old.stride(0), x_len_old.data_ptr(), t_x_old,
+        x_len_new.data_ptr(), t_x_new, spans.data_ptr(), _ptr(span_given), _ptr(span_target),
+        y_len_old.data_ptr(), given.data_ptr(), target.data_ptr(), meta.data_ptr(), B,
+        _stream_ptr(dev)), "vits_edit_pins")
+    return given, target, meta
+
+
+def edit_splice(dur_new: torch.Tensor, spans: torch.Tensor, y_len_old: torch.Tensor,
+                m_p: torch.Tensor, s_p: torch.Tensor, noise: torch.Tensor, z_p_rec: torch.Tensor,
+                *, x_len: Optional[torch.Tensor] = None, stage_mult=(1,),
+                out: Optional[torch.Tensor] = None):
+    """The spliced latents of an edit in one pass (vits_edit_splice): the
+    recording's ``z_p_rec`` fp32 [B, C, t_rec] outside the edited frames, the
+    prior expansion m_p + noise * s_p of the new span under ``dur_new`` (int32
+    [B, t_x], ``duration_plan``'s) between them, zero past y_new.  ``m_p`` /
+    ``s_p`` [B, C, t_x]; ``noise`` fp32 [B, C, t_y], pre-scaled and indexed by
+    output frame, fixes the bucket t_y.  Returns (z fp32 [B, C, t_y], lens
+    int32 [n_stage, B] = y_new * stage_mult, meta int32 [4, B] = f0 | n_new |
+    f1 | status); status -1: y_new > t_y, 1: an inconsistent span; the row is
+    then zero with length 0."""
+    what = "edit_splice"
+    require_device(dur_new, m_p, s_p, noise, z_p_rec)
+    B, C_, t_x = m_p.shape
+    dur_new = _durations_arg(dur_new, B, t_x, 1.0, False, what)
+    i32 = torch.int32
+    spans = _edit_arg(what, spans, i32, (B, 3), "spans")
+    y_len_old = _edit_arg(what, y_len_old, i32, (B,), "y_len_old")
+    x_len = _edit_arg(what, x_len, i32, (B,), "x_len", True)
+    if noise.dim() != 3 or tuple(noise.shape[:2]) != (B, C_):
+        raise _lib.VitsAmdError(f"{what}: noise must be fp32 [{B}, {C_}, t_y]")
+    t_y = noise.shape[2]
+    noise = _edit_arg(what, noise, torch.float32, (B, C_, t_y), "noise")
+    if z_p_rec.dim() != 3:
+        raise _lib.VitsAmdError(f"{what}: z_p_rec must be fp32 [{B}, {C_}, t_rec]")
+    t_rec = z_p_rec.shape[2]
+    z_p_rec = _edit_arg(what, z_p_rec, torch.float32, (B, C_, t_rec), "z_p_rec")
+    m_p = m_p.float().contiguous()
+    s_p = s_p.float().contiguous()
+    dev = m_p.device
+    if out is None:
+        out = torch.empty(B, C_, t_y, device=dev, dtype=torch.float32)
+    _edit_arg(what, out, torch.float32, (B, C_, t_y), "out")
+    n_stage = len(stage_mult)
+    lens = torch.empty(n_stage, B, device=dev, dtype=i32)
+    meta = torch.empty(4, B, device=dev, dtype=i32)
+    mult = (C.c_int32 * n_stage)(*[int(v) for v in stage_mult])
+    check(_lib.load().vits_edit_splice(
+        dur_new.data_ptr(), dur_new.stride(0), _ptr(x_len), t_x, spans.data_ptr(),
+        y_len_old.data_ptr(), m_p.data_ptr(), s_p.data_ptr(), m_p.stride(0), m_p.stride(1),
+        noise.data_ptr(), z_p_rec.data_ptr(), t_rec, out.data_ptr(), B, C_, t_y, lens.data_ptr(),
+        mult, n_stage, meta.data_ptr(), _stream_ptr(dev)), "vits_edit_splice")
+    return out, lens, meta
+
+
+def edit_patch(orig: torch.Tensor, o: torch.Tensor, y_len_old: torch.Tensor,
+               splice_meta: torch.Tensor, hop: int, *, margin: int, fade: int,
+               out: Optional[torch.Tensor] = None):
+    """The waveform side of an edit (vits_edit_patch states the arithmetic):
+    the recording ``orig`` fp32 [B, n] (at the model rate) outside the edited
+    frames widened by ``margin`` frames, the synthesis ``o`` fp32 [B, n_o]
+    inside, a linear cross-fade of ``fade`` samples at each seam, the
+    recording's tail shifted by the change of length.  ``splice_meta`` is
+    edit_splice's.  Rows may be strided.  Returns (out fp32 [B, n_o], out_len
+    int32 [B] = y_new * hop); a row that cannot be patched is zero with length
+    0."""
+    what = "edit_patch"
+    require_device(orig, o, y_len_old, splice_meta)
+    for name, t in (("orig", orig), ("o", o)):
+        if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            raise _lib.VitsAmdError(f"{what}: {name} must be fp32 [B, n] with contiguous rows")
+    B = o.shape[0]
+    if orig.shape[0] != B:
+        raise _lib.VitsAmdError(f"{what}: orig has {orig.shape[0]} rows, o {B}")
+    y_len_old = _edit_arg(what, y_len_old, torch.int32, (B,), "y_len_old")
+    splice_meta = _edit_arg(what, splice_meta, torch.int32, (4, B), "splice_meta")
+    if out is None:
+        out = torch.empty(B, o.shape[1], device=o.device, dtype=torch.float32)
+    _edit_arg(what, out, torch.float32, (B, out.shape[1] if out.dim() == 2 else -1), "out")
+    out_len = torch.empty(B, device=o.device, dtype=torch.int32)
+    check(_lib.load().vits_edit_patch(
+        orig.data_ptr(), orig.stride(0), orig.shape[1], o.data_ptr(), o.stride(0), o.shape[1],
+        y_len_old.data_ptr(), splice_meta.data_ptr(), int(hop), int(margin), int(fade),
+        out.data_ptr(), out.stride(0), out.shape[1], out_len.data_ptr(), B,
+        _stream_ptr(o.device)), "vits_edit_patch")
+    return out, out_len

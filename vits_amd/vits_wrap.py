@@ -326,6 +326,63 @@ class VITSWrap(object):
         return self._with_durations(out, dur)
 
     @torch.no_grad()
+    def editing(self, inputs: dict) -> dict:
+        """Speech-editing request: {"wav" (the recording, int16 or float
+        samples), "sampling_rate_in", "spkid", "text" (what the recording
+        says), "text_new" (what it should say), "emotion", "duration_s" (the
+        re-spoken span lasts round(s * rate / hop) frames) or "keep_length"
+        (it lasts what the replaced span did), "patch" (default True: the
+        recording's own samples outside the edit), and the output fields of
+        ``converting``} -> the dict of ``converting`` plus "durations" (int32
+        [Tx_new], the frames per token of the result), "boundaries_s",
+        "scores" (float32 [Tx_old], the alignment's) and "span_s": {"old":
+        (start, end), "new": (start, end)}, the edited region in seconds of
+        the recording and of the result at the model's rate.  The span is the
+        one EmoVITS.edit_span finds between the two vector sequences.  Both
+        texts must be one segment each; needs device_post=True on a ROCm GPU
+        (EmoVITS.edit_pcm)."""
+        if not self.device_post:
+            raise ValueError("VITSWrap.editing needs device_post=True on a ROCm GPU")
+        inputs, utt_id, utt_text, spkid, volume, _, pitch, sampling_rate, tail_silence, emotion = \
+            self._parse_input(inputs)
+        if "wav" not in inputs or "text_new" not in inputs:
+            raise ValueError("editing needs the recording (wav), its text and text_new")
+        parsed = []
+        for what, text in (("text", utt_text), ("text_new", inputs["text_new"])):
+            ids, texts = self._split_utt_text(utt_id, text)
+            if len(texts) != 1:
+                raise ValueError(f"editing: {what} splits into {len(texts)} segments of at most "
+                                 f"{self.max_utt_length} characters; one segment per recording")
+            parsed.append((ids[0], texts[0]))
+        sp = self.speecher
+        span_frames = None
+        if inputs.get("duration_s") is not None and inputs.get("keep_length"):
+            raise ValueError("editing: give duration_s or keep_length, not both")
+        if inputs.get("keep_length"):
+            span_frames = "keep"
+        elif inputs.get("duration_s") is not None:
+            sec = float(inputs["duration_s"])
+            if not np.isfinite(sec) or sec <= 0:
+                raise ValueError(f"editing: duration_s must be a positive number, got {sec}")
+            span_frames = int(round(sec * sp.sampling_rate / sp.hop_size))
+            if span_frames < 1:
+                raise ValueError(f"editing: duration_s = {sec} is less than one frame")
+        rec = inputs.pop("wav")
+        t0 = time.time()
+        (_, segtext, vec_old), (_, segtext_new, vec_new) = [self.textparser(i, t) for i, t in parsed]
+        t1 = time.time()
+        pcm, n_model, dur, (f0, n_new, f1), scores = sp.edit_pcm(
+            rec, spkid, vec_old, vec_new, emotion, sampling_rate_in=inputs.get("sampling_rate_in"),
+            span_frames=span_frames, patch=bool(inputs.get("patch", True)), pitch=pitch,
+            sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence)
+        out = self._finish(inputs, [parsed[1][1]], [segtext_new], [len(pcm)], [pcm], n_model,
+                           sampling_rate, t1 - t0, time.time() - t1)
+        sec = sp.hop_size / sp.sampling_rate
+        out["scores"] = scores
+        out["span_s"] = {"old": (f0 * sec, f1 * sec), "new": (f0 * sec, (f0 + n_new) * sec)}
+        return self._with_durations(out, dur)
+
+    @torch.no_grad()
     def aligning(self, inputs: dict) -> dict:
         """Forced-alignment request: {"wav" (int16 or float samples), "text",
         "spkid", "emotion", "sampling_rate_in", "id"} -> the same dict plus
