@@ -41,7 +41,10 @@
  *   vits_resample_poly /     the output stage of VITSWrap.speaking
  *   vits_pcm16               (vits_wrap.py:186-197): librosa.resample for
  *                            pitch and sampling rate, clip, int16, tail pad
- *   vits_draw_starts         the np.random.randint slice starts of
+ *   vits_resample_poly_span  a span of that stage's output from a window of
+ *                            its input: the chunks of a streamed utterance
+ *                            (no counterpart: the reference sends whole files)
+ *   vits_draw_starts        the np.random.randint slice starts of
  *                            consecutive EmoVITS.infer calls (infer.py:173),
  *                            for a whole batch in call order
  *   vits_pack_pcm            the segment concatenation of VITSWrap.speaking
@@ -1072,6 +1075,32 @@ int vits_resample_poly(const void* x, int x_dtype, int64_t x_bstride, int x_cap,
 int vits_pcm16(const void* x, int x_dtype, int64_t x_bstride, int x_cap, const int32_t* lens,
                int len_scale, int n_host, float volume, int16_t* pcm, int64_t out_bstride,
                int out_cap, int batch, void* stream);
+
+/* vits_resample_poly_span: one row, one pass of the output stage over a   */
+/* SPAN of the whole signal's output, from a WINDOW of its input (streamed */
+/* synthesis).  x holds the samples [x_lo, x_lo + x_len) of  */
+/* a signal of n_in samples; out[j], j < out_len, is output sample out_lo  */
+/* + j of vits_resample_poly over the whole signal, bit for bit: the phase */
+/* follows the global index and the sum is the same fp32 FMA chain in      */
+/* ascending k over the inputs in [0, n_in) (the zero taps that pad a      */
+/* phase row are not read).  Samples at or past n_out = ceil(n_in * up /   */
+/* down) are written as zero up to out_len (the tail silence).  table,     */
+/* table_rows, table_k, up, down, half_len, out / pcm and volume as for    */
+/* vits_resample_poly; up == down == 1 is the copy (vits_pcm16 over a      */
+/* span).  All offsets and lengths are host integers, counted in samples   */
+/* of the whole signal.  VITS_E_ARG: a null pointer (x may be NULL only    */
+/* with x_len == 0), a negative offset or size, both or neither output.    */
+/* VITS_E_SHAPE: a table that is not this ratio's, an index beyond int64,  */
+/* or a tap of a requested output that needs an input in [0, n_in) outside */
+/* the window: that input range is, for the outputs [out_lo, e), e =       */
+/* min(out_lo + out_len, n_out), [max(0, ceil((out_lo * down - half_len) / */
+/* up)), min(n_in, floor(((e - 1) * down + half_len) / up) + 1)), or       */
+/* [out_lo, e) for the copy.  Nothing outside x[0, x_len) is read; out_len */
+/* == 0 launches nothing.                                                  */
+int vits_resample_poly_span(const void* x, int x_dtype, int64_t x_lo, int64_t x_len, int64_t n_in,
+                            const float* table, int table_rows, int table_k, int up, int down,
+                            int half_len, float* out, int16_t* pcm, int64_t out_lo,
+                            int64_t out_len, float volume, void* stream);
 
 /* Ragged pack behind the last pass (a request's segments in one copy):    */
 /* rows int16 [batch][cap] (row stride bstride) -> out int16 [out_cap]:     */

@@ -535,6 +535,11 @@ _SIGS = {
         [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
          C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p],
     ),
+    "vits_resample_poly_span": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p] + [C.c_int] * 5
+        + [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p],
+    ),
     "vits_pack_pcm": (
         C.c_int,
         [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

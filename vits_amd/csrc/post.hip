@@ -38,6 +38,17 @@ __device__ __forceinline__ void post_st(int16_t* p, int64_t i, float v, float vo
   p[i] = (int16_t)(int)s;
 }
 
+// The FMA chain of one output sample: taps k_lo .. k_hi of its phase row
+// against the inputs xr[i0 - k], ascending k.  The whole-signal kernels and
+// the span kernel both call it, so a sample is the same bits in either.
+template <typename XT>
+__device__ __forceinline__ float post_chain(const XT* __restrict__ xr, int64_t i0,
+                                            const float* __restrict__ row, int k_lo, int k_hi) {
+  float acc = 0.f;
+  for (int k = k_lo; k <= k_hi; ++k) acc = fmaf(post_ld(xr, i0 - k), row[k], acc);
+  return acc;
+}
+
 // Output sample blockIdx.x * 256 + threadIdx.x of row b = blockIdx.y, whose
 // input length is n_in before clamping: the one place the arithmetic of the
 // output stage lives (the uniform and the per-row kernel both call it).
@@ -66,7 +77,7 @@ __device__ __forceinline__ void post_row_sample(
       // input i0 - k must lie in [0, n_in)
       const int k_lo = (int)max((int64_t)0, i0 - (n_in - 1));
       const int k_hi = (int)min((int64_t)(K - 1), i0);
-      for (int k = k_lo; k <= k_hi; ++k) acc = fmaf(post_ld(xr, i0 - k), row[k], acc);
+      acc = post_chain(xr, i0, row, k_lo, k_hi);
     }
   }
   post_st(out + (int64_t)b * out_bstride, n, acc, volume);
@@ -81,6 +92,58 @@ __global__ __launch_bounds__(256) void post_resample_kernel(
   const int64_t n_in = lens ? (int64_t)lens[blockIdx.y] * len_scale : (int64_t)n_host;
   post_row_sample(x, x_bstride, x_cap, n_in, table, K, up, down, half_len, out, out_bstride,
                   out_cap, volume, out_lens);
+}
+
+// ---------------------------------------------------------------------------
+// Span form (streaming): out[j] = output sample out_lo + j of the whole
+// signal of n_in samples, computed from a window x that holds its samples
+// [x_lo, x_lo + x_len).  The phase and the newest input follow the GLOBAL
+// index n = out_lo + j; the chain is post_chain over the same taps as the
+// whole-signal kernel, minus the zero taps that pad a phase row to K (their
+// inputs may lie outside the window; a zero tap leaves the sum as it is).
+// Zero from n_out on.  The host has checked that every input read lies in
+// the window.
+// ---------------------------------------------------------------------------
+template <typename XT, typename OT>
+__global__ __launch_bounds__(256) void post_span_kernel(
+    const XT* __restrict__ x, int64_t x_lo, int64_t n_in, const float* __restrict__ table, int K,
+    int up, int down, int half_len, OT* __restrict__ out, int64_t out_lo, int64_t out_len,
+    float volume) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= out_len) return;
+  const int64_t n = out_lo + j;
+  const int64_t n_out = (n_in * up + down - 1) / down;
+  float acc = 0.f;
+  if (n < n_out) {
+    if (!table) {
+      acc = post_ld(x, n - x_lo);
+    } else {
+      const int64_t c = n * down + half_len;
+      const int64_t i0 = c / up;
+      const int r = (int)(c - i0 * up);
+      const float* row = table + (int64_t)r * K;
+      // input i0 - k must lie in [0, n_in), tap r + k * up in [0, 2 * half_len]
+      const int k_lo = (int)max((int64_t)0, i0 - (n_in - 1));
+      const int k_hi = (int)min((int64_t)((2 * half_len - r) / up), i0);
+      acc = post_chain(x, i0 - x_lo, row, k_lo, k_hi);
+    }
+  }
+  post_st(out, j, acc, volume);
+}
+
+template <typename XT>
+int post_span_launch(const void* x, int64_t x_lo, int64_t n_in, const float* table, int K, int up,
+                     int down, int half_len, float* out, int16_t* pcm, int64_t out_lo,
+                     int64_t out_len, float volume, hipStream_t s) {
+  const dim3 grid((unsigned)((out_len + 255) / 256));
+  const XT* xp = reinterpret_cast<const XT*>(x);
+  if (pcm)
+    hipLaunchKernelGGL((post_span_kernel<XT, int16_t>), grid, dim3(256), 0, s, xp, x_lo, n_in,
+                       table, K, up, down, half_len, pcm, out_lo, out_len, volume);
+  else
+    hipLaunchKernelGGL((post_span_kernel<XT, float>), grid, dim3(256), 0, s, xp, x_lo, n_in, table,
+                       K, up, down, half_len, out, out_lo, out_len, volume);
+  return vits_launch_status();
 }
 
 // ---------------------------------------------------------------------------
@@ -391,6 +454,61 @@ extern "C" int vits_resample_poly(const void* x, int x_dtype, int64_t x_bstride,
   return post_dispatch(x, x_dtype, x_bstride, x_cap, lens, len_scale, n_host, table, table_k, up,
                        down, half_len, out, pcm, out_bstride, out_cap, volume, out_lens, batch,
                        stream);
+}
+
+extern "C" int vits_resample_poly_span(const void* x, int x_dtype, int64_t x_lo, int64_t x_len,
+                                       int64_t n_in, const float* table, int table_rows,
+                                       int table_k, int up, int down, int half_len, float* out,
+                                       int16_t* pcm, int64_t out_lo, int64_t out_len, float volume,
+                                       void* stream) {
+  VITS_CHECK_ARG(up >= 1 && down >= 1);
+  VITS_CHECK_ARG(x_lo >= 0 && x_len >= 0 && n_in >= 0 && out_lo >= 0 && out_len >= 0);
+  VITS_CHECK_ARG(x || x_len == 0);
+  VITS_CHECK_ARG((out != nullptr) != (pcm != nullptr));
+  VITS_CHECK_ARG(x_dtype == VITS_DT_F32 || x_dtype == VITS_DT_F16 || x_dtype == VITS_DT_BF16);
+  if (up == 1 && down == 1) {
+    table = nullptr;  // scipy returns a copy: no filter
+    half_len = table_k = 0;
+  } else {
+    // the phase table must be the one of this ratio (see post_dispatch)
+    VITS_CHECK_ARG(table);
+    VITS_CHECK_SHAPE(table_rows == up);
+    VITS_CHECK_SHAPE(half_len == 10 * (up > down ? up : down));
+    VITS_CHECK_SHAPE(table_k == (2 * half_len + up) / up);
+  }
+  // every index the kernel forms fits int64, and the grid its 32-bit x extent
+  VITS_CHECK_SHAPE(x_lo <= INT64_MAX - x_len && out_lo <= INT64_MAX - out_len);
+  VITS_CHECK_SHAPE(n_in <= (INT64_MAX - down) / up);
+  VITS_CHECK_SHAPE(out_lo + out_len <= (INT64_MAX - half_len) / down);
+  VITS_CHECK_SHAPE((out_len + 255) / 256 <= INT32_MAX);
+  // the inputs in [0, n_in) under a tap of any requested output below n_out
+  // (both ends grow with n: the first output gives the lowest input, the
+  // last one the highest); ops.resample_span_input is this arithmetic
+  const int64_t n_out = (n_in * up + down - 1) / down;
+  const int64_t n_end = out_lo + out_len < n_out ? out_lo + out_len : n_out;
+  if (out_lo < n_end) {
+    int64_t need_lo = out_lo, need_hi = n_end;
+    if (table) {
+      const int64_t first = out_lo * down - half_len;
+      need_lo = first <= 0 ? 0 : (first + up - 1) / up;
+      need_hi = ((n_end - 1) * down + half_len) / up + 1;
+      need_hi = need_hi < n_in ? need_hi : n_in;
+    }
+    if (need_lo < need_hi) VITS_CHECK_SHAPE(x_lo <= need_lo && need_hi <= x_lo + x_len);
+  }
+  if (out_len == 0) return VITS_OK;
+  const hipStream_t s = as_stream(stream);
+  switch (x_dtype) {
+    case VITS_DT_F16:
+      return post_span_launch<_Float16>(x, x_lo, n_in, table, table_k, up, down, half_len, out,
+                                        pcm, out_lo, out_len, volume, s);
+    case VITS_DT_BF16:
+      return post_span_launch<__bf16>(x, x_lo, n_in, table, table_k, up, down, half_len, out, pcm,
+                                      out_lo, out_len, volume, s);
+    default:
+      return post_span_launch<float>(x, x_lo, n_in, table, table_k, up, down, half_len, out, pcm,
+                                     out_lo, out_len, volume, s);
+  }
 }
 
 extern "C" int vits_pcm16(const void* x, int x_dtype, int64_t x_bstride, int x_cap,

@@ -61,6 +61,43 @@ class _Window(NamedTuple):
     core_off: int  # samples into the row at which the core starts
 
 
+class _Chunk(NamedTuple):
+    """One chunk of a streamed utterance (EmoVITS._stream_plan)."""
+    core_lo: int  # it owns the frames [core_lo, core_hi) of the utterance
+    core_hi: int
+    a: int  # its decoder window spans the frames [a, b)
+    b: int
+    out_lo: int  # and it yields the output samples [out_lo, out_hi) (the last: tail included)
+    out_hi: int
+    # per pass of the output stage: (in_lo, in_hi, out_lo, out_hi), the span of
+    # the pass's output the chunk computes and the exact range of its input
+    # that needs (ops.resample_span_input); with no pass, the one copy pass
+    passes: tuple
+
+
+class PcmStream(object):
+    """What EmoVITS.infer_pcm_stream returns: an iterator over the int16
+    chunks of one utterance.  Known before the first chunk exists:
+    ``n_samples`` (all chunks together, tail silence included), ``n_model``
+    (samples at the model's rate), ``durations`` (int32 [Tx] frames per
+    token; None for a call without duration controls or return_durations)
+    and ``emo``.  ``close()`` drops the chunks not yet taken; the engine
+    stays usable and numpy's generator is where a complete call leaves it."""
+
+    def __init__(self, chunks, n_samples, n_model, durations, emo):
+        self._chunks = chunks
+        self.n_samples, self.n_model, self.durations, self.emo = n_samples, n_model, durations, emo
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._chunks)
+
+    def close(self):
+        self._chunks.close()
+
+
 class EmoVITS(object):
     def __init__(self, checkpoint_path=None, device=None, *, loglv=0, hps=None, model=None,
                  graph_cache=0, graph=True, max_graphs=16, half=True):
@@ -201,11 +238,13 @@ class EmoVITS(object):
         cache[key] = run  # most recently used last
         return run
 
-    def _capture_synthesis(self, xb, tyb, **kw):
-        """A whole-utterance graph (capture_infer_bucketed over padded text)
-        that reads this object's noise buffer."""
-        run = self.model.capture_infer_bucketed(xb, tyb, noise_len=self.noise.numel(),
-                                                padded_text=True, **kw)
+    def _capture_synthesis(self, xb, tyb, front=False, **kw):
+        """A whole-utterance graph (capture_infer_bucketed over padded text;
+        ``front``: capture_infer_front_bucketed, the text side alone) that
+        reads this object's noise buffer."""
+        capture = (self.model.capture_infer_front_bucketed if front
+                   else self.model.capture_infer_bucketed)
+        run = capture(xb, tyb, noise_len=self.noise.numel(), padded_text=True, **kw)
         run.static["noise"].copy_(self.noise.float())
         return run
 
@@ -289,9 +328,11 @@ class EmoVITS(object):
         d, _ = dur_host.plan_durations(w.float().view(-1).cpu().numpy(), given, target)
         return torch.from_numpy(d.astype(np.float32)).to(logw.device).view(1, 1, -1)
 
-    def _infer_eager(self, x_length, text_t, emo, sid, duration_rate, ctl=None, got=None):
+    def _infer_eager(self, x_length, text_t, emo, sid, duration_rate, ctl=None, got=None,
+                     front=False):
         """The reference's sequence: infer_p1 -> host durations -> infer_p2;
-        the waveform stays on the device."""
+        the waveform stays on the device.  ``front``: infer_p2 stops behind
+        the flow (infer_p2_front) and (z [1, C, y_length], g) is returned."""
         m_p, s_p, logw, g = self._infer_p1(text_t, emo, sid)
         w_ceil = self._host_durations(logw, duration_rate, ctl)
         if got is not None:
@@ -304,6 +345,8 @@ class EmoVITS(object):
         start = np.random.randint(max(1, self.noise.size(0) - nl))
         noise = self.noise[start:start + nl].view(1, self.inter_channels, y_length)
         attn = infer_path(w_ceil.float(), x_length, y_length).to(self.dtype)
+        if front:
+            return self.model.infer_p2_front(attn, m_p, s_p, g, noise), g
         return self.model.infer_p2(attn, m_p, s_p, g, noise)
 
     def _post_passes(self, pitch, sampling_rate):
@@ -430,6 +473,233 @@ class EmoVITS(object):
             n = wav.shape[-1]
             pcm = self._post(wav.reshape(1, -1), out, lengths=n)
         return pcm[0, :self._n_out(n, out.passes) + out.tail].cpu().numpy(), n
+
+    # -- streaming: the front once, the decoder and the output stage per chunk (4w) --
+    # the window buckets whose cores are the default first and later chunk
+    # sizes (measured: profiles/stream_latency.txt)
+    STREAM_FIRST_WINDOW, STREAM_WINDOW = 256, 2048
+    STREAM_MIN_WINDOW = 64
+
+    def _stream_sizes(self, first_chunk_frames, chunk_frames, ctx):
+        """The core sizes of a streamed call: the given ones, or windows of
+        STREAM_FIRST_WINDOW and STREAM_WINDOW frames less 2 * ctx of context.
+        ValueError for a size below one frame."""
+        first = (max(1, self.STREAM_FIRST_WINDOW - 2 * ctx) if first_chunk_frames is None
+                 else int(first_chunk_frames))
+        chunk = (max(first, self.STREAM_WINDOW - 2 * ctx) if chunk_frames is None
+                 else int(chunk_frames))
+        if first < 1 or chunk < 1:
+            raise ValueError(f"streaming needs chunks of at least one frame, got first_chunk_frames"
+                             f"={first}, chunk_frames={chunk}")
+        return first, chunk
+
+    @classmethod
+    def _stream_bucket(cls, frames):
+        """The window bucket of a decoder window: a power of two, at least
+        STREAM_MIN_WINDOW."""
+        return max(cls.STREAM_MIN_WINDOW, 1 << max(0, int(frames) - 1).bit_length())
+
+    def _stream_plan(self, y_len, out, first_chunk_frames, chunk_frames, context):
+        """The chunks of an utterance of ``y_len`` frames under the output
+        controls ``out`` (_output), for decoder windows with ``context`` frames
+        between an artificial edge and what must be exact
+        (Generator.context_frames).  Chunk k owns the core frames [s_k, e_k):
+        ``first_chunk_frames`` of them, then twice the last size up to
+        ``chunk_frames``; the cores partition [0, y_len).  Its output span is
+        the core's samples [s_k * hop, e_k * hop) taken forwards through the
+        passes (n -> ceil(n * up / down), so the spans partition [0, n_out));
+        the last chunk also owns the tail.  From the last pass back to the
+        first, ops.resample_span_input gives the exact range of each pass's
+        input that span needs; the frames that hold the first pass's range
+        join the core, and the window is that with ``context`` frames on each
+        side, cut at 0 and y_len: the utterance's own edges, where the
+        whole-utterance decoder is cut too.  Host arithmetic only; ValueError
+        for y_len, a chunk size below 1 or a negative context."""
+        hop = self.hop_size
+        y_len, first, chunk, ctx = (int(y_len), int(first_chunk_frames), int(chunk_frames),
+                                    int(context))
+        if y_len < 1 or first < 1 or chunk < 1 or ctx < 0:
+            raise ValueError(f"no stream plan for {y_len} frames in chunks of {first} / {chunk} "
+                             f"frames with {ctx} frames of context")
+        passes = out.passes or [(1, 1)]
+        lens = [y_len * hop]
+        for up, down in passes:
+            lens.append(ops.resample_out_len(lens[-1], up, down))
+        plan, s, size = [], 0, first
+        while s < y_len:
+            e = min(y_len, s + size)
+            lo, hi = s * hop, e * hop
+            for up, down in passes:
+                lo, hi = ops.resample_out_len(lo, up, down), ops.resample_out_len(hi, up, down)
+            if e == y_len:
+                hi += out.tail
+            spans, need = [], (lo, hi)
+            for i in reversed(range(len(passes))):
+                src = ops.resample_span_input(need[0], need[1], lens[i], *passes[i])
+                spans.append(src + need)
+                need = src
+            f_lo, f_hi = s, e
+            if need[0] < need[1]:  # the frames under the first pass's input join the core
+                f_lo, f_hi = min(s, need[0] // hop), max(e, -(-need[1] // hop))
+            plan.append(_Chunk(s, e, max(0, f_lo - ctx), min(y_len, f_hi + ctx), lo, hi,
+                               tuple(reversed(spans))))
+            s, size = e, min(2 * size, chunk)
+        return plan
+
+    def infer_pcm_stream(self, spkid, text, emo, *, first_chunk_frames=None, chunk_frames=None,
+                         duration_rate=1.0, pitch=1.0, sampling_rate=None, volume=1.0,
+                         tail_silence=0.0, durations=None, token_scale=None, target_frames=None,
+                         return_durations=False):
+        """infer_pcm, streamed: a PcmStream whose int16 chunks, end to end,
+        are the array infer_pcm returns for the same call, sample for sample
+        (an fp16 model at the base config: to its decoder's rounding,
+        DESIGN.md 4w), with numpy's generator left where infer_pcm leaves it.
+        The text side runs ONCE, as a replay of the front graph (text
+        encoder, durations, draw, prior expansion, reverse flow: cached under
+        ("front", ...) beside the utterance graphs, same buckets and re-run);
+        the host then reads y_len, the call's one extra sync, so the stream's
+        ``n_samples``, ``n_model`` and ``durations`` are set when this call
+        returns, before any audio exists.  Then, per chunk of _stream_plan:
+        ops.copy_windows moves the window of z into the static input of the
+        decode graph cached under ("dec", window bucket), the graph replays,
+        the span passes of the output stage (ops.resample_poly_span /
+        resample_pcm16_span) run behind it and one device-to-host copy brings
+        the chunk's int16.  Chunk k + 1 is enqueued before chunk k's copy is
+        waited for (two PCM buffers, an event per chunk; the stream is never
+        synchronised).
+
+        ``first_chunk_frames`` / ``chunk_frames``: the first core and the
+        largest; the cores double in between.  Default: the cores of 256- and
+        2048-frame windows.  ValueError below one frame.  graph=False or text
+        past 4096 tokens: the same plan through the eager functions.  A CPU
+        device: infer_pcm, sliced on the plan's boundaries.  The other
+        arguments as in infer_pcm."""
+        out = self._output(pitch, sampling_rate, volume, tail_silence)
+        ctx = self.model.dec.context_frames()
+        first, chunk = self._stream_sizes(first_chunk_frames, chunk_frames, ctx)
+        ctl = self._controls(text.shape[0], durations, token_scale, target_frames,
+                             return_durations)  # (refuses before anything is uploaded)
+        x_length, text_t, emo, sid = self._inputs(spkid, text, emo)
+        return self._stream_one(x_length, text_t, emo, sid, duration_rate, out, ctl, first, chunk,
+                                ctx)
+
+    def infer_pcm_streams(self, items, *, first_chunk_frames=None, chunk_frames=None,
+                          duration_rate=1.0, pitch=1.0, sampling_rate=None, volume=1.0,
+                          tail_silence=0.0, batch=True):
+        """infer_pcm_stream for items = [(spkid, text, emo), ...] that share
+        their controls (the segments of a request): one PcmStream per item,
+        whose chunks are what infer_pcm_batch returns for it.  EVERY front
+        runs before this returns, so all lengths are known before any audio
+        exists; ``batch``: groups of up to MAX_BATCH items as ONE replay of a
+        batched front graph (the rows and draws of infer_pcm_batch), else one
+        front replay per item.  The chunks of each stream are then decoded as
+        it is iterated, in any order.  Emotion lookups and numpy's generator
+        as infer_pcm_batch."""
+        out = self._output(pitch, sampling_rate, volume, tail_silence)
+        ctx = self.model.dec.context_frames()
+        first, chunk = self._stream_sizes(first_chunk_frames, chunk_frames, ctx)
+        texts, spkids, emos = self._resolve_items(items)
+        streams = []
+        for lo, hi in self._groups(len(texts)):
+            if not batch or hi - lo == 1 or not self._batchable(texts[lo:hi]):
+                for i in range(lo, hi):
+                    x_length, text_t, sid = self._one_tensors(spkids[i], texts[i])
+                    streams.append(self._stream_one(x_length, text_t, emos[i], sid, duration_rate,
+                                                    out, None, first, chunk, ctx))
+                continue
+            (z, g), y = self._infer_graph_batch(texts[lo:hi], emos[lo:hi], spkids[lo:hi],
+                                                duration_rate, front=True)
+            for i, n in enumerate(y):
+                chunks = self._stream_latents(z[i:i + 1], g[i:i + 1], n, out, first, chunk, ctx)
+                streams.append(PcmStream(
+                    chunks, self._n_out(n * self.hop_size, out.passes) + out.tail,
+                    n * self.hop_size, None, emos[lo + i]))
+        return streams
+
+    def _stream_one(self, x_length, text_t, emo, sid, duration_rate, out, ctl, first, chunk, ctx):
+        """The front of one utterance, now, and the PcmStream of its chunks."""
+        got = [] if ctl is not None else None
+        hop = self.hop_size
+        if self.device.type != "cuda":
+            pcm, n = self._infer_pcm_one(x_length, text_t, emo, sid, duration_rate, out, ctl, got)
+            y_len = n // hop
+            plan = self._stream_plan(y_len, out, first, chunk, ctx)
+            chunks = (pcm[c.out_lo:c.out_hi] for c in plan if c.out_hi > c.out_lo)
+        else:
+            if self.graph and x_length <= 4096:
+                (z, g), y_len = self._infer_graph(text_t, emo, sid, duration_rate, ctl=ctl,
+                                                  got=got, front=True)
+            else:
+                z, g = self._infer_eager(x_length, text_t, emo, sid, duration_rate, ctl, got,
+                                         front=True)
+                y_len = z.shape[2]
+            chunks = self._stream_latents(z, g, y_len, out, first, chunk, ctx)
+        return PcmStream(chunks, self._n_out(y_len * hop, out.passes) + out.tail, y_len * hop,
+                         got[0] if got else None, emo)
+
+    def _stream_latents(self, z, g, y_len, out, first, chunk, ctx):
+        """The chunk generator over row 0 of a front's (z [., C, >= y_len], g):
+        both are copied out of the graph's static buffers, so that another
+        call on this engine between two chunks changes nothing."""
+        z = z[:1, :, :y_len].float().clone(memory_format=torch.contiguous_format)
+        return self._stream_chunks(z, g[:1].clone(), y_len,
+                                   self._stream_plan(y_len, out, first, chunk, ctx), out)
+
+    def _stream_chunks(self, z, g, y_len, plan, out):
+        """The chunks of ``plan`` over z [1, C, y_len] (infer_pcm_stream
+        documents the order of work)."""
+        passes = out.passes or [(1, 1)]
+        lens = [y_len * self.hop_size]
+        for up, down in passes:
+            lens.append(ops.resample_out_len(lens[-1], up, down))
+        plan = [c for c in plan if c.out_hi > c.out_lo]
+        cap = max([1] + [c.out_hi - c.out_lo for c in plan])
+        dev = [torch.empty(cap, device=self.device, dtype=torch.int16) for _ in range(2)]
+        host = [torch.empty(cap, dtype=torch.int16, pin_memory=True) for _ in range(2)]
+        done = [torch.cuda.Event() for _ in range(2)]
+        pending = None
+        for k, c in enumerate(plan):
+            slot, n = k % 2, c.out_hi - c.out_lo
+            with torch.no_grad():
+                self._stream_enqueue(z, g, c, passes, lens, out.volume, dev[slot])
+                host[slot][:n].copy_(dev[slot][:n], non_blocking=True)
+            done[slot].record(torch.cuda.current_stream(self.device))
+            if pending is not None:
+                done[pending[0]].synchronize()
+                yield host[pending[0]][:pending[1]].numpy().copy()
+            pending = (slot, n)
+        if pending is not None:
+            done[pending[0]].synchronize()
+            yield host[pending[0]][:pending[1]].numpy().copy()
+
+    def _stream_enqueue(self, z, g, c, passes, lens, volume, pcm):
+        """Chunk c on the current stream: window copy, decoder, span passes;
+        its int16 samples land in pcm[:c.out_hi - c.out_lo].  No sync."""
+        hop, C = self.hop_size, self.inter_channels
+        w = c.b - c.a
+        W = self._stream_bucket(w)
+        if self.graph:
+            dec = self._cached_graph(("dec", W), lambda: self.model.capture_decode_window(W))
+            z_win = dec.static["z"]
+            dec.static["g"].copy_(g)
+        else:
+            z_win = torch.empty(1, C, W, device=self.device)
+        ops.copy_windows(z, z_win, [(c.a, 0, w, W)], channels=C, src_rstride=z.shape[2],
+                         dst_rstride=W)
+        if self.graph:
+            wav = dec(w)
+        else:
+            wav = self.model.decode_window_bucketed(
+                z_win, torch.tensor([w], dtype=torch.int32, device=self.device), g)
+        x, x_lo = wav.reshape(-1)[:w * hop], c.a * hop
+        for i, (up, down) in enumerate(passes):
+            o_lo, o_hi = c.passes[i][2:]
+            if i == len(passes) - 1:
+                ops.resample_pcm16_span(x, x_lo, lens[i], up, down, o_lo, o_hi - o_lo, volume,
+                                        out=pcm)
+            else:
+                x = ops.resample_poly_span(x, x_lo, lens[i], up, down, o_lo, o_hi - o_lo)
+                x_lo = o_lo
 
     # -- batched serving: all segments of a request in one utterance graph --------
     MAX_BATCH = 16
@@ -738,7 +1008,7 @@ class EmoVITS(object):
         return buf[:n].numpy().copy()
 
     def _infer_graph_batch(self, texts, emos, spkids, duration_rate, post=None, rates=None,
-                           ctls=None, got=None):
+                           ctls=None, got=None, front=False):
         """2..16 utterances as one replay of a batched utterance graph, cached
         with the B = 1 graphs per (batch bucket, text bucket, frame bucket,
         rate); with ``rates`` (one speed per row; ``duration_rate`` unused)
@@ -761,7 +1031,12 @@ class EmoVITS(object):
         rows whose total the host knows need.  The final durations [B, text
         bucket] ride behind the header words of the packed buffer (``post``
         gets them as ``extra``, None for a plain group), or with the words when
-        there is no post, and row i's int32 [t_x_i] is appended to ``got``."""
+        there is no post, and row i's int32 [t_x_i] is appended to ``got``.
+
+        ``front`` (no post): the group replays the batched front graph
+        (capture_infer_front_bucketed, cached under ("front",) + the key above)
+        and ((z [B, C, frames], g [B, gin]), y_len list) is returned, views of
+        the graph's static buffers."""
         n = len(texts)
         controlled = ctls is not None and any(c is not None for c in ctls)
         if controlled and rates is None:
@@ -789,8 +1064,10 @@ class EmoVITS(object):
             key = (bb, xb, tyb, float(duration_rate)) if rates is None else ("rows", bb, xb, tyb)
             if controlled:
                 key = ("ctl", bb, xb, tyb)
+            if front:
+                key = ("front",) + key
             run = self._cached_graph(key, lambda: self._capture_synthesis(
-                xb, tyb, batch=bb, control=controlled,
+                xb, tyb, front=front, batch=bb, control=controlled,
                 length_scale=duration_rate if rates is None else torch.ones(bb)))
             pool, state = ops.numpy_draw_pool(run.pool_len * pool_mult)
             if pool_mult == 1:
@@ -799,12 +1076,15 @@ class EmoVITS(object):
                 # the graph's pool is static: the (p < 2^-32 per row) longer
                 # pool runs the same kernels eagerly on the graph's inputs
                 st = run.static
-                res = self.model.infer_bucketed(
+                infer = self.model.infer_front_bucketed if front else self.model.infer_bucketed
+                res = infer(
                     st["x"], st["emo"], st["sid"], st["noise"], tyb, x_lengths=st["xl"],
                     length_scale=duration_rate if rates is None else st["rates"],
                     noise_start=torch.from_numpy(pool).to(self.device), n_rows=st["n_rows"],
                     control={k: st[k] for k in ("given", "tok_scale", "target")}
                     if controlled else None)
+            if front:
+                head, res = res[:2], res[1:]
             wav, words, dur = res[0], res[1:4], res[4] if controlled else None
             if post is None:
                 host = torch.cat(words + ((dur.reshape(-1),) if controlled else ())).tolist()
@@ -825,6 +1105,8 @@ class EmoVITS(object):
             if controlled and got is not None:
                 d = np.asarray(d, np.int32).reshape(bb, xb)
                 got += [d[i, :lengths[i]].copy() for i in range(n)]
+            if front:
+                return head, y
             return (wav, y) if post is None else ((pcm, offs), y)
 
     # -- voice conversion: waveform in, waveform out --------------------------------
@@ -1774,7 +2056,8 @@ class EmoVITS(object):
         return ValueError(f"utterance of {n} frames does not fit the "
                           f"{self.noise.numel()}-sample noise buffer")
 
-    def _infer_graph(self, text_t, emo, sid, duration_rate, post=None, ctl=None, got=None):
+    def _infer_graph(self, text_t, emo, sid, duration_rate, post=None, ctl=None, got=None,
+                     front=False):
         """One replay of the whole-utterance graph; the one host sync is the
         waveform copy (y_len read with it).  A bucket that turns out too
         small (y_len > frames) is re-run once at a large enough bucket,
@@ -1790,7 +2073,12 @@ class EmoVITS(object):
         the host knows the total (a target, or every token pinned) the frame
         bucket is chosen from it; else the bucket is remembered per text
         bucket and grown by the re-run below.  ``got`` (a list): the final
-        durations (int32 [t_x]) are appended to it."""
+        durations (int32 [t_x]) are appended to it.
+
+        ``front``: the replay is the front graph of a streamed utterance
+        (capture_infer_front_bucketed, cached under ("front",) + the key the
+        whole-utterance graph has): the same buckets, re-run and draw commit;
+        returns ((z [1, C, bucket], g), frames), views of static buffers."""
         t_x = text_t.shape[1]
         xb = self._text_bucket(t_x)
         memo = (xb, duration_rate) if ctl is None else ("ctl", xb)
@@ -1799,18 +2087,22 @@ class EmoVITS(object):
             if ctl is not None and ctl[3] is not None:
                 tyb = self._frame_bucket(ctl[3])
             key = (xb, tyb, float(duration_rate)) if ctl is None else ("ctl", 1, xb, tyb)
+            if front:
+                key = ("front",) + key
             run = self._cached_graph(key, lambda: self._capture_synthesis(
-                xb, tyb, length_scale=duration_rate, control=ctl is not None))
+                xb, tyb, front=front, length_scale=duration_rate, control=ctl is not None))
             # infer.py:173's np.random.randint(len - nl), drawn on the device
             # from raw words of numpy's own generator: the same start as the
             # reference, and the generator ends where the reference's does
             pool, state = ops.numpy_draw_pool()
             if ctl is None:
-                wav, y_len = run(text_t, emo, sid, noise_start=pool, x_length=t_x)
+                res = run(text_t, emo, sid, noise_start=pool, x_length=t_x)
             else:
-                wav, y_len, dur, _ = run(
-                    text_t, emo, sid, noise_start=pool, x_length=t_x, rate=duration_rate,
-                    control=dict(given=ctl[0], tok_scale=ctl[1], target=ctl[2]))
+                res = run(text_t, emo, sid, noise_start=pool, x_length=t_x, rate=duration_rate,
+                          control=dict(given=ctl[0], tok_scale=ctl[1], target=ctl[2]))
+            head, res = (res[:2], res[2:]) if front else (res[:1], res[1:])
+            wav, y_len = head[0], res[0]
+            dur = res[1] if ctl is not None else None
             posted = None if post is None else post(wav[0], y_len[0])
             if ctl is None:
                 n, used = (int(v) for v in y_len[:, 0].tolist())  # (synchronises)
@@ -1830,6 +2122,8 @@ class EmoVITS(object):
                 if used < 0:
                     raise self._misfit(state, n)
                 ops.numpy_draw_commit(state, used)
+                if front:
+                    return head, n
                 if post is not None:
                     return posted, n
                 return wav[0, 0, :n * self.hop_size].float().cpu().numpy()

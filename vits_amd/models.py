@@ -584,14 +584,19 @@ class SynthesizerTrn(nn.Module):
     def infer_p2(self, attn, m_p, s_p, g, noise):
         """Acoustic side (models.py:568-575): prior expansion + noise, reverse
         flow, decoder — all libvits_amd kernels."""
+        z = self.infer_p2_front(attn, m_p, s_p, g, noise)
+        gplan = engine.get_plan(self.dec, engine.GeneratorPlan)
+        o = gplan.run(z, engine._f32(g))
+        return o.to(m_p.dtype)
+
+    @torch.no_grad()
+    def infer_p2_front(self, attn, m_p, s_p, g, noise):
+        """infer_p2 up to and including the reverse flow: z fp32 [B, C, t_y],
+        the decoder's input."""
         engine._check_gpu(m_p, "SynthesizerTrn.infer_p2")
         z = engine.ops.expand_prior(attn, m_p, s_p, noise)
-        fplan = engine.get_plan(self.flow, engine.CouplingFlowPlan)
-        gf = engine._f32(g)
-        fplan.run_(z, gf)
-        gplan = engine.get_plan(self.dec, engine.GeneratorPlan)
-        o = gplan.run(z, gf)
-        return o.to(m_p.dtype)
+        engine.get_plan(self.flow, engine.CouplingFlowPlan).run_(z, engine._f32(g))
+        return z
 
     # stage multipliers of the lengths the bucketed infer hands to the flow,
     # conv_pre and the upsample stages (frames -> samples after each ups)
@@ -651,7 +656,38 @@ class SynthesizerTrn(nn.Module):
         int32 [2, B] = total | status) as its last two values; each row is bit
         for bit infer_durations of its returned durations.  None: nothing
         changes and no further kernel is launched."""
-        engine._check_gpu(x, "SynthesizerTrn.infer_bucketed")
+        z, g, dt, lens, draw, plan = self._front(
+            "infer_bucketed", x, emo, sid, noise, t_y, x_lengths, length_scale, noise_start,
+            n_rows, control)
+        with engine.ops.length_skip(64):
+            o = engine.get_plan(self.dec, engine.GeneratorPlan).run(z, engine._f32(g),
+                                                                    lengths=lens[1:])
+        return (o.to(dt),) + draw + plan
+
+    @torch.no_grad()
+    def infer_front_bucketed(self, x, emo, sid, noise, t_y, *, x_lengths=None, length_scale=1.0,
+                             noise_start=None, n_rows=None, control=None):
+        """infer_bucketed up to and including the reverse flow (the text
+        side of a streamed utterance): the same arguments, the
+        same kernels in the same order, no decoder.  Returns (z fp32 [B, C,
+        t_y], the decoder's input, masked at y_len; g [B, gin] in the model's
+        dtype) followed by what infer_bucketed returns after its waveform:
+        y_len (int32 [B], or [2, B] with the draw status under
+        ``noise_start``; y_len, status, used_total in the shared-pool form)
+        and, with ``control``, (dur, plan_meta).  decode_window_bucketed
+        over windows of z gives the samples infer_bucketed gives."""
+        z, g, _, _, draw, plan = self._front(
+            "infer_front_bucketed", x, emo, sid, noise, t_y, x_lengths, length_scale, noise_start,
+            n_rows, control)
+        return (z, g) + draw + plan
+
+    def _front(self, what, x, emo, sid, noise, t_y, x_lengths, length_scale, noise_start, n_rows,
+               control):
+        """The text side of infer_bucketed (documented there): text encoder,
+        durations, draw, prior expansion, reverse flow.  Returns (z, g, the
+        model's dtype, stage lengths int32 [n, B], the length / draw results
+        as a tuple, the duration plan's as a tuple)."""
+        engine._check_gpu(x, "SynthesizerTrn." + what)
         rate = length_scale if isinstance(length_scale, torch.Tensor) else float(length_scale)
         dt = x.dtype
         shared_pool = noise_start is not None and noise_start.dim() == 1
@@ -690,15 +726,69 @@ class SynthesizerTrn(nn.Module):
         z, lens = engine.ops.expand_durations(
             logw, m_p, s_p, noise, int(t_y), x_len=xl, noise_start=noise_start,
             stage_mult=self._stage_mult(), starts=starts, **src)
-        gf = engine._f32(g)
         with engine.ops.length_skip(64):
-            engine.get_plan(self.flow, engine.CouplingFlowPlan).run_(z, gf, lengths=lens[0])
-            o = engine.get_plan(self.dec, engine.GeneratorPlan).run(z, gf, lengths=lens[1:])
+            engine.get_plan(self.flow, engine.CouplingFlowPlan).run_(z, engine._f32(g),
+                                                                     lengths=lens[0])
         if shared_pool:
-            return (o.to(m_p.dtype), y_len, status, used_total) + plan
-        if noise_start is not None:
-            return (o.to(m_p.dtype), lens[0::len(lens) - 1]) + plan
-        return (o.to(m_p.dtype), lens[0]) + plan
+            draw = (y_len, status, used_total)
+        elif noise_start is not None:
+            draw = (lens[0::len(lens) - 1],)
+        else:
+            draw = (lens[0],)
+        return z, g, m_p.dtype, lens, draw, plan
+
+    @torch.no_grad()
+    def decode_window_bucketed(self, z_win, win_len, g):
+        """The decoder over one window of a streamed utterance: z_win fp32
+        [B, C, W] holds frames [a, a + win_len) of infer_front_bucketed's z,
+        zero past win_len (int32 [B] on the device); g as the front returns
+        it.  GeneratorPlan.run masked at win_len under ops.length_skip(64),
+        as infer_bucketed runs it at y_len: a window that ends at y_len sees
+        the utterance's own end, one that starts at frame 0 its own start,
+        and a sample Generator.context_frames() frames from any other edge is
+        the whole utterance's.  No host sync.  Returns [B, 1, W * hop] in
+        g's dtype (the model's, as infer_bucketed's waveform); samples at or
+        past win_len * hop are not meaningful."""
+        engine._check_gpu(z_win, "SynthesizerTrn.decode_window_bucketed")
+        mult = self.__dict__.get("_win_mult")
+        if mult is None or mult.device != z_win.device:
+            mult = self.__dict__["_win_mult"] = torch.tensor(
+                self._stage_mult()[1:], device=z_win.device, dtype=torch.int32).view(-1, 1)
+        lens = mult * win_len.view(1, -1)
+        with engine.ops.length_skip(64):
+            o = engine.get_plan(self.dec, engine.GeneratorPlan).run(z_win, engine._f32(g),
+                                                                    lengths=lens)
+        return o.to(g.dtype)
+
+    @torch.no_grad()
+    def capture_decode_window(self, W, warmup=2):
+        """One hipGraph for decode_window_bucketed over a window bucket of W
+        frames.  It depends on no text: one graph per W serves every
+        utterance.  Returns run(win_len) -> wav [1, 1, W * hop] (a view of a
+        static buffer) for a caller that has written ``run.static["z"]`` [1,
+        C, W] (ops.copy_windows straight from the front's z, zero-filled to
+        W) and ``run.static["g"]`` [1, gin] itself; win_len is a host int."""
+        dev = next(self.parameters()).device
+        dt = next(self.parameters()).dtype
+        W = int(W)
+        static = dict(z=torch.zeros(1, self.inter_channels, W, device=dev),
+                      g=torch.zeros(1, self.emb_g.embedding_dim, device=dev, dtype=dt),
+                      n=torch.full((1,), W, device=dev, dtype=torch.int32))
+        self.decode_window_bucketed(static["z"], static["n"], static["g"])  # (builds the plan)
+
+        def body():
+            return self.decode_window_bucketed(static["z"], static["n"], static["g"])
+
+        graph, out = self._capture_body(body, warmup, dev)
+
+        def run(win_len):
+            if not 1 <= int(win_len) <= W:
+                raise ValueError(f"decode replay: {win_len} frames do not fit a window of {W}")
+            static["n"].fill_(int(win_len))
+            graph.replay()
+            return out
+
+        return self._graph_run(run, graph, static, t_y=W)
 
     # ------------------------------------------------------------ hipGraphs
     # Every capture_* below is the same three steps: static input buffers, a
@@ -731,7 +821,7 @@ class SynthesizerTrn(nn.Module):
     @torch.no_grad()
     def capture_infer_bucketed(self, t_x, t_y, *, noise_len=None, padded_text=False,
                                length_scale=1.0, warmup=2, batch=1, pool_len=None,
-                               control=False):
+                               control=False, _front=False):
         """One hipGraph for a whole utterance (infer_bucketed) of t_x tokens
         (padded_text: up to t_x, x_lengths given at replay) into a t_y-frame
         bucket.  noise_len: replay reads a flat noise buffer of that many
@@ -770,7 +860,7 @@ class SynthesizerTrn(nn.Module):
             length_scale = torch.full((int(batch),), float(length_scale))
         if batch > 1:
             return self._capture_infer_batch(t_x, t_y, int(batch), noise_len, padded_text,
-                                             length_scale, warmup, pool_len, control)
+                                             length_scale, warmup, pool_len, control, _front)
         dev = next(self.parameters()).device
         dt = next(self.parameters()).dtype
         C = self.inter_channels
@@ -784,13 +874,14 @@ class SynthesizerTrn(nn.Module):
             static["rates"] = length_scale.to(device=dev, dtype=torch.float32).reshape(1).clone()
         ctl = _control_buffers(static, 1, t_x, dev) if control else None
 
+        infer = self.infer_front_bucketed if _front else self.infer_bucketed
+
         def body():
             noise = static["noise"] if noise_len else static["noise"].view(1, C, t_y)
-            return self.infer_bucketed(static["x"], static["emo"], static["sid"], noise, t_y,
-                                       x_lengths=static["xl"] if padded_text else None,
-                                       length_scale=static.get("rates", length_scale),
-                                       noise_start=static["start"] if noise_len else None,
-                                       control=ctl)
+            return infer(static["x"], static["emo"], static["sid"], noise, t_y,
+                         x_lengths=static["xl"] if padded_text else None,
+                         length_scale=static.get("rates", length_scale),
+                         noise_start=static["start"] if noise_len else None, control=ctl)
 
         graph, out = self._capture_body(body, warmup, dev)
 
@@ -822,8 +913,19 @@ class SynthesizerTrn(nn.Module):
 
         return self._graph_run(run, graph, static, t_y=t_y)
 
+    @torch.no_grad()
+    def capture_infer_front_bucketed(self, t_x, t_y, *, noise_len=None, padded_text=False,
+                                     length_scale=1.0, warmup=2, batch=1, pool_len=None,
+                                     control=False):
+        """capture_infer_bucketed for infer_front_bucketed: the same static
+        buffers and the same ``run``, whose result starts with (z [batch, C,
+        t_y], g [batch, gin]) in place of the waveform."""
+        return self.capture_infer_bucketed(
+            t_x, t_y, noise_len=noise_len, padded_text=padded_text, length_scale=length_scale,
+            warmup=warmup, batch=batch, pool_len=pool_len, control=control, _front=True)
+
     def _capture_infer_batch(self, t_x, t_y, batch, noise_len, padded_text, length_scale, warmup,
-                             pool_len, control=False):
+                             pool_len, control=False, front=False):
         """capture_infer_bucketed for batch > 1 (see there)."""
         if not padded_text or not noise_len:
             raise ValueError("capture_infer_bucketed: batch > 1 needs padded_text=True and noise_len")
@@ -843,12 +945,12 @@ class SynthesizerTrn(nn.Module):
         cols = torch.arange(t_x, device=dev).view(1, t_x, 1)
         ctl = _control_buffers(static, batch, t_x, dev) if control else None
 
+        infer = self.infer_front_bucketed if front else self.infer_bucketed
+
         def body():
-            return self.infer_bucketed(static["x"], static["emo"], static["sid"], static["noise"],
-                                       t_y, x_lengths=static["xl"],
-                                       length_scale=static.get("rates", length_scale),
-                                       noise_start=static["pool"], n_rows=static["n_rows"],
-                                       control=ctl)
+            return infer(static["x"], static["emo"], static["sid"], static["noise"], t_y,
+                         x_lengths=static["xl"], length_scale=static.get("rates", length_scale),
+                         noise_start=static["pool"], n_rows=static["n_rows"], control=ctl)
 
         graph, out = self._capture_body(body, warmup, dev)
 

@@ -2056,6 +2056,86 @@ def pcm16(x: torch.Tensor, volume: float = 1.0, *, lengths=None, length_scale: i
     return _post_launch("pcm16", x, 1, 1, lengths, length_scale, out, None, volume, True)
 
 
+# -- span form: a stretch of the whole signal's output from a window of its input --
+
+
+def resample_span_input(out_lo: int, out_hi: int, n_in: int, up: int, down: int,
+                        half_len: Optional[int] = None) -> tuple[int, int]:
+    """The exact input range [i_lo, i_hi) that the output samples [out_lo,
+    out_hi) of resample_poly over a signal of ``n_in`` samples depend on: the
+    inputs in [0, n_in) under one of the 2 * half_len + 1 taps of an output
+    below n_out = resample_out_len(n_in, up, down) (outputs at or past n_out
+    are zero and need nothing).  Output n reads the inputs i with 0 <= n *
+    down - i * up + half_len <= 2 * half_len; both ends grow with n.  up ==
+    down (the copy) needs [out_lo, min(out_hi, n_in)).  An empty need is (i,
+    i).  ``half_len`` defaults to the filter's 10 * max(up, down), which is
+    what a given value must equal.  Host integers only; this is the check
+    vits_resample_poly_span makes on its window."""
+    up, down = _reduced(up, down)
+    out_lo, out_hi, n_in = int(out_lo), int(out_hi), int(n_in)
+    if out_lo < 0 or out_hi < out_lo or n_in < 0:
+        raise _lib.VitsAmdError(f"resample_span_input: bad span [{out_lo}, {out_hi}) of {n_in}")
+    hl = 0 if up == down else 10 * max(up, down)
+    if half_len is not None and up != down and int(half_len) != hl:
+        raise _lib.VitsAmdError(f"resample_span_input: half_len of {up}/{down} is {hl}, got "
+                                f"{half_len}")
+    end = min(out_hi, resample_out_len(n_in, up, down))
+    if end <= out_lo:
+        i = out_lo if up == down else 0
+        return i, i
+    if up == down:
+        return out_lo, end
+    lo = max(0, -(-(out_lo * down - hl) // up))
+    hi = min(n_in, ((end - 1) * down + hl) // up + 1)
+    return (lo, hi) if lo < hi else (lo, lo)
+
+
+def _span_launch(what, x, x_lo, n_in, up, down, out_lo, out_len, out, volume, pcm):
+    require_device(x, out)
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise _lib.VitsAmdError(f"{what}: x must be fp32, fp16 or bf16, got {x.dtype}")
+    if x.dim() != 1 or x.stride(0) != 1:
+        raise _lib.VitsAmdError(f"{what}: x must be a window [x_len] with unit stride")
+    up, down = _reduced(up, down)
+    out_len = int(out_len)
+    odt = torch.int16 if pcm else torch.float32
+    if out is None:
+        out = torch.empty(max(0, out_len), device=x.device, dtype=odt)
+    if out.dtype != odt or out.dim() != 1 or out.stride(0) != 1 or out.numel() < out_len:
+        raise _lib.VitsAmdError(f"{what}: out must be {odt} [>= {out_len}] with unit stride")
+    table, half_len = (None, 0) if up == down else resample_filter(up, down, x.device)
+    check(_lib.load().vits_resample_poly_span(
+        x.data_ptr() if x.numel() else None, _DT[x.dtype], int(x_lo), x.numel(), int(n_in),
+        _ptr(table), up, 0 if table is None else table.shape[1], up, down, half_len,
+        None if pcm else out.data_ptr(), out.data_ptr() if pcm else None, int(out_lo), out_len,
+        float(volume), _stream_ptr(x.device)), what)
+    return out[:out_len]
+
+
+def resample_poly_span(x: torch.Tensor, x_lo: int, n_in: int, up: int, down: int, out_lo: int,
+                       out_len: int, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The samples [out_lo, out_lo + out_len) of resample_poly(whole, up,
+    down) over a signal of ``n_in`` samples, bit for bit, from the window
+    ``x`` [x_len] (fp32 / fp16 / bf16) that holds its samples [x_lo, x_lo +
+    x_len): fp32 [out_len], zero from n_out on.  The window must hold
+    resample_span_input(out_lo, out_lo + out_len, n_in, up, down); a shorter
+    one is refused and nothing outside it is read.  Every offset is a host
+    integer; with ``out`` given and the filter cached the call allocates
+    nothing.  up == down is the copy."""
+    return _span_launch("resample_poly_span", x, x_lo, n_in, up, down, out_lo, out_len, out, 1.0,
+                        False)
+
+
+def resample_pcm16_span(x: torch.Tensor, x_lo: int, n_in: int, up: int, down: int, out_lo: int,
+                        out_len: int, volume: float = 1.0, *,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """resample_poly_span with the int16 epilogue of pcm16: the same span of
+    resample_pcm16 over the whole signal (int16, silence from n_out on); up
+    == down is the span form of pcm16."""
+    return _span_launch("resample_pcm16_span", x, x_lo, n_in, up, down, out_lo, out_len, out,
+                        volume, True)
+
+
 PACK_MAX_BATCH = 64  # post.hip PK_MAX_BATCH
 
 

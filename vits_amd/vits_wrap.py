@@ -231,6 +231,49 @@ class VITSWrap(object):
         return self._finish(inputs, texts, segtexts, seg_samples, batch_wav, batch_wavlen,
                             sampling_rate, t_front, t_back)
 
+    def speaking_stream(self, inputs: dict):
+        """``speaking``, streamed: an iterator of bytes whose first item is
+        the 44-byte RIFF header with the exact final length and whose items,
+        joined, are ``speaking(inputs)["wav"]``, byte for byte, with numpy's
+        generator left where ``speaking`` leaves it.  The front end and the
+        text side of EVERY segment run before this returns (one batched
+        front replay with batch_segments=True, else one per segment), so the
+        header is exact before any audio exists; the segments' chunks then
+        follow in order as they are decoded (EmoVITS.infer_pcm_stream), each
+        segment's tail silence in its last chunk.  ``first_chunk_frames`` /
+        ``chunk_frames`` in the request set the chunk sizes; ``durations`` /
+        ``token_scale`` / ``duration_s`` control a one-segment text as in
+        ``speaking``.  Needs device_post=True on a ROCm GPU."""
+        if not self.device_post:
+            raise ValueError("VITSWrap.speaking_stream needs device_post=True on a ROCm GPU")
+        inputs, utt_id, utt_text, spkid, volume, speed, pitch, sampling_rate, tail_silence, emotion = \
+            self._parse_input(inputs)
+        ids, texts = self._split_utt_text(utt_id, utt_text)
+        ctl = self._duration_controls(inputs, len(texts), "speaking_stream")
+        parsed = [self.textparser(uid, text) for uid, text in zip(ids, texts)]
+        sp = self.speecher
+        kw = dict(first_chunk_frames=inputs.get("first_chunk_frames"),
+                  chunk_frames=inputs.get("chunk_frames"), duration_rate=speed, pitch=pitch,
+                  sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence)
+        with torch.no_grad():
+            if ctl is not None:
+                ctl = {k: v for k, v in ctl.items() if k != "return_durations"}
+                streams = [sp.infer_pcm_stream(spkid, parsed[0][2], emotion, **kw, **ctl)]
+            else:
+                # one emotion lookup for the request, before every noise draw (speaking's order)
+                _, emotion = sp._resolve(spkid, emotion)
+                streams = sp.infer_pcm_streams(
+                    [(spkid, vec, emotion) for _, _, vec in parsed],
+                    batch=self.batch_segments and len(texts) >= self.BATCH_MIN_SEGMENTS, **kw)
+
+        def items():
+            yield _gen_wav_header(sum(s.n_samples for s in streams), sampling_rate, 16)
+            for s in streams:
+                for chunk in s:
+                    yield chunk.tobytes()
+
+        return items()
+
     def _finish(self, inputs, texts, segtexts, seg_samples, batch_wav, batch_wavlen, sampling_rate,
                 t_front, t_back):
         """The result dict of ``speaking`` (vits_wrap.py:199-218)."""
