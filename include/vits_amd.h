@@ -58,6 +58,9 @@
  *                            on the device
  *   vits_*_int               vits_expand_durations / vits_draw_starts from
  *                            those integer durations
+ *   vits_retime_plan /       a recording's own latents resampled along time,
+ *   vits_retime_warp         token by token (no counterpart: the reference
+ *                            converts a recording at its own length only)
  */
 #ifndef VITS_AMD_H
 #define VITS_AMD_H
@@ -1273,6 +1276,81 @@ int vits_edit_patch(const float* orig, int64_t orig_bstride, int orig_cap, const
                     int64_t o_bstride, int o_cap, const int32_t* y_len_old,
                     const int32_t* splice_meta, int hop, int margin, int fade, float* out,
                     int64_t out_bstride, int out_cap, int32_t* out_len, int batch, void* stream);
+
+/* ---------------------------------------------------------------------- */
+/* Retiming a recording: the recording's own latents are     */
+/* resampled along time, token by token.  All lengths are read on the       */
+/* device, no call keeps a host pointer, both can be captured.  Durations   */
+/* and pins are taken as min(max(d, 0), 2^18), the clamp of the _int entry  */
+/* points.                                                                  */
+/*                                                                          */
+/* vits_retime_plan (one 256-thread workgroup per row): a row's old         */
+/* durations dur_old int32 [batch] rows of dur_old_bstride (token x <       */
+/* x_len[b], NULL: t_x) to its new ones.  Optional (NULL = none): given     */
+/* int32 [batch][t_x] (>= 0 pins the token to that many frames, < 0 leaves  */
+/* it free), tok_scale fp32 [batch][t_x] (NULL: 1), rate fp32 [batch]       */
+/* (NULL: 1), target int32 [batch] (> 0: the row lasts exactly that many    */
+/* frames, <= 0: none).  With F = the free tokens and P = the sum of the    */
+/* pins, in token order over F:                                             */
+/*   s[x]  = fminf(fmaxf(tok_scale[x] * rate, 2^-8), 2^8)   one fp32        */
+/*           product; rate is taken as 1 when the row has a target; a NaN   */
+/*           becomes 2^-8                                                   */
+/*   q[x]  = llrint((double)dur_old[x] * (double)s[x] * 256.0)   (exact: 42 */
+/*           significant bits; ties to even)                                */
+/*   Q[x]  = inclusive prefix sum of q over F, Qtot = its last (int64)      */
+/*   E     = target ? target - P : (Qtot + 128) >> 8                        */
+/*   B[x]  = (Q[x] * E + Qtot / 2) / Qtot       (int64 division; Qtot == 0: */
+/*           every B is 0)                                                  */
+/*   d[x]  = B[x] - B[previous free token]      (B = 0 before the first)    */
+/*   dur_new[x] = pin, or d[x]; 0 for x_len <= x < t_x                      */
+/* so that the free tokens sum to E exactly, a free token may get 0 frames, */
+/* nothing depends on a summation order, and with no control q = 256 *      */
+/* dur_old, E = sum(dur_old) and dur_new == dur_old.  A consistent row has  */
+/* Qtot <= 2^34 and E <= 2^26 (2^24 with a target): Q * E <= 2^60.          */
+/* meta int32 [2][batch] = total (the sum of dur_new) | status.  status 1   */
+/* (the row gets dur_new = dur_old): sum(dur_old[:x_len]) != y_len_old,     */
+/* y_len_old > 2^18, E < 0, target > 2^24, or a target with Qtot == 0 and   */
+/* E != 0.                                                                  */
+/* VITS_E_ARG: NULL dur_old / y_len_old / dur_new / meta, batch <= 0, t_x   */
+/* <= 0; VITS_E_SHAPE: dur_old_bstride < t_x; VITS_E_UNSUP: t_x > 4096.     */
+/* ---------------------------------------------------------------------- */
+int vits_retime_plan(const int32_t* dur_old, int64_t dur_old_bstride, const int32_t* x_len,
+                     int t_x, const int32_t* y_len_old, const int32_t* given,
+                     const float* tok_scale, const float* rate, const int32_t* target,
+                     int32_t* dur_new, int32_t* meta, int batch, void* stream);
+
+/* vits_retime_warp (256 threads per 64 output frames of a row): z_p_rec    */
+/* fp32 [batch][channels][t_rec], read below y_len_old only, to z fp32      */
+/* [batch][channels][t_y], every element written.  c_old / c_new = the      */
+/* exclusive prefix sums of dur_old / dur_new (rows of their bstride, token */
+/* x < x_len[b], NULL: t_x), y_new = sum(dur_new).  For t < y_new, with i   */
+/* the token that owns frame t (c_new[i] <= t < c_new[i] + dur_new[i];      */
+/* tokens of 0 new frames own nothing), k = t - c_new[i], dn = dur_new[i],  */
+/* do = dur_old[i], in int64:                                               */
+/*   num = (2k + 1) * do - dn, den = 2 * dn                                 */
+/*   qf = floor(num / den), r = num - qf * den                              */
+/*   j0 = clamp(c_old[i] + qf, 0, y_len_old - 1)                            */
+/*   j1 = clamp(c_old[i] + qf + 1, 0, y_len_old - 1)                        */
+/*   w  = (float)r / (float)den        (exact operands, one correctly       */
+/*        rounded fp32 division)                                            */
+/*   z[t] = (r == 0 || j0 == j1) ? z_p_rec[j0]                              */
+/*        : z_p_rec[j0] + w * (z_p_rec[j1] - z_p_rec[j0])                   */
+/* a rounded subtraction, product and sum (no contraction); z[t] = 0 for    */
+/* y_new <= t < t_y.  This is the centre-aligned piecewise-linear map of    */
+/* each token's new frames onto its old ones ((k + 1/2) * do / dn - 1/2),   */
+/* continuous across token boundaries, the exact copy where dn == do.       */
+/* lens int32 [n_stage][batch] = y_new * stage_mult[i] (NULL with n_stage   */
+/* 1: 1); meta int32 [2][batch] = y_new | status.  status -1: y_new > t_y,  */
+/* y_len_old <= 0 or y_len_old > t_rec; the row is then zero and its lens   */
+/* are 0, meta still reports y_new.                                         */
+/* VITS_E_ARG: a NULL pointer other than x_len, a z or z_p_rec off a 4-byte */
+/* boundary, a size <= 0, n_stage outside [1, 8]; VITS_E_UNSUP: t_x > 4096, */
+/* t_rec or t_y > 2^18; VITS_E_SHAPE: a bstride < t_x, batch > 65535.       */
+int vits_retime_warp(const float* z_p_rec, int t_rec, const int32_t* dur_old,
+                     int64_t dur_old_bstride, const int32_t* dur_new, int64_t dur_new_bstride,
+                     const int32_t* x_len, int t_x, const int32_t* y_len_old, float* z, int batch,
+                     int channels, int t_y, int32_t* lens, const int32_t* stage_mult, int n_stage,
+                     int32_t* meta, void* stream);
 
 /* library introspection */
 const char* vits_amd_version(void);

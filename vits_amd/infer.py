@@ -1818,6 +1818,215 @@ class EmoVITS(object):
         n = y_new * self.hop_size
         return pcm[0, :self._n_out(n, out.passes) + out.tail].cpu().numpy(), n, dur, pos, scores
 
+    # -- retiming a recording: speed, fitted length, per-token timing
+    RETIME_MIN_SCALE, RETIME_MAX_SCALE = 1.0 / 16, 16.0
+
+    def _retime_check(self, n_in, sampling_rate_in, speed, pitch, target_frames, text, durations,
+                      token_scale, durations_old):
+        """Everything about a retiming the host can refuse before anything is
+        uploaded (ValueError): returns (frames, tokens (0: text-free), given
+        int32 [tokens] or None, scale fp32 [tokens] or None, target,
+        durations_old int32 [tokens] or None, the durations' rate = speed /
+        pitch, the host bound on y_new)."""
+        lo, hi = self.RETIME_MIN_SCALE, self.RETIME_MAX_SCALE
+        frames = self._vc_plan(n_in, sampling_rate_in)[2]  # (over VC_MAX_FRAMES: ValueError)
+
+        def in_range(name, v):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) \
+                    or not np.isfinite(v) or not lo <= float(v) <= hi:
+                raise ValueError(f"{name} must be a finite number in [1/16, 16], got {v!r}")
+            return float(v)
+
+        rate = in_range("speed / pitch", in_range("speed", speed) / float(pitch))
+        if text is None and (durations is not None or token_scale is not None):
+            raise ValueError("durations and token_scale are per token: they need text")
+        n_tok = 0 if text is None else int(text.shape[0])
+        if durations_old is not None:
+            durations_old = np.asarray(durations_old).reshape(-1).astype(np.int32)
+            if text is None:
+                n_tok = int(durations_old.shape[0])
+            if (durations_old.shape[0] != n_tok or n_tok < 1 or bool((durations_old < 0).any())
+                    or int(durations_old.sum()) != frames):
+                raise ValueError(f"durations_old must be {n_tok} frame counts >= 0 that sum to "
+                                 f"the recording's {frames} frames")
+        if text is not None and (n_tok < 1 or frames < n_tok):
+            raise ValueError(f"recording of {frames} frames cannot be aligned with {n_tok} "
+                             "tokens: every token takes at least one frame")
+        if n_tok > self.ALIGN_MAX_TOKENS:
+            raise ValueError(f"text of {n_tok} tokens exceeds the alignment kernel's "
+                             f"{self.ALIGN_MAX_TOKENS}")
+        target = 0
+        if target_frames is not None:
+            if isinstance(target_frames, bool) or not isinstance(target_frames, (int, np.integer)) \
+                    or not 0 < target_frames <= self.VC_MAX_FRAMES:
+                raise ValueError(f"target_frames must be an int in 1 .. {self.VC_MAX_FRAMES}, got "
+                                 f"{target_frames!r}")
+            target = int(target_frames)
+        given = None
+        if durations is not None:
+            d = np.asarray(durations).reshape(-1)
+            if d.shape[0] != n_tok:
+                raise ValueError(f"durations need {n_tok} values (< 0: free), got {d.shape[0]}")
+            given = np.where(d < 0, -1, np.minimum(d, 1 << 18)).astype(np.int32)
+        scale = None
+        if token_scale is not None:
+            scale = np.asarray(token_scale, np.float32).reshape(-1)
+            if scale.shape[0] != n_tok or not bool(np.all(np.isfinite(scale))) or not bool(
+                    np.all((scale >= lo) & (scale <= hi))):
+                raise ValueError(f"token_scale needs {n_tok} finite factors in [1/16, 16]")
+        if target:
+            bound = target
+        else:
+            pins = 0 if given is None else int(given[given >= 0].sum())
+            top = 1.0 if scale is None else float(scale.max())
+            bound = int(np.ceil(frames * float(rate) * top)) + max(n_tok, 1) + pins
+        if bound > self.VC_MAX_FRAMES:
+            raise ValueError(f"the retimed recording may take {bound} frames: more than the "
+                             f"largest bucket of {self.VC_MAX_FRAMES} frames")
+        return frames, n_tok, given, scale, target, durations_old, rate, bound
+
+    def _retime_rows(self, wav, spkid_src, spkid_tgt, speed, pitch, target_frames, text, emo,
+                     durations, token_scale, durations_old, sampling_rate_in, noise_scale,
+                     post=None):
+        """One retiming through one graph, cached in self._graphs under
+        ("retime", 1, text bucket or 0, recording frame bucket, output frame
+        bucket, durations_old given) (graph=False: the same retime_bucketed
+        call, eagerly, on the same padded inputs).  The output bucket holds a
+        host bound on y_new, so no re-run is ever needed.  Returns (wav_out
+        [1, n] fp32 on the device, or ``post(wav_out, lengths,
+        length_scale)``'s result; y_new; dur_old; dur_new; scores) after ONE
+        small device-to-host copy (meta, both duration rows and the scores)."""
+        stft = self._vc_begin("retime")
+        hop = self.hop_size
+        text = None if text is None else np.ascontiguousarray(text)
+        n_in = np.asarray(wav).reshape(-1).shape[0]
+        frames, n_tok, given, scale, target, durations_old, rate, bound = self._retime_check(
+            n_in, sampling_rate_in, speed, pitch, target_frames, text, durations, token_scale,
+            durations_old)
+        src, tgt = self._map_spkid(spkid_src), self._map_spkid(spkid_tgt)
+        x, lens, _, trb, _, noise = self._vc_upload([wav], sampling_rate_in, noise_scale)
+        aligned = text is not None and durations_old is None
+        xt = e = None
+        if aligned:
+            e = self._resolve(spkid_src, emo)[1]
+            xt = self._text_rows([text], [n_tok])
+        xb = self._text_bucket(n_tok) if n_tok else 0
+        tw, nt = max(xb, 1), max(n_tok, 1)
+        tyb = self._frame_bucket(bound)
+        dev, i32 = self.device, torch.int32
+        g_row = np.full(tw, -1, np.int32)
+        if given is not None:
+            g_row[:n_tok] = given
+        s_row = np.ones(tw, np.float32)
+        if scale is not None:
+            s_row[:n_tok] = scale
+        d_row = None
+        if durations_old is not None:
+            d_row = np.zeros(xb, np.int32)
+            d_row[:n_tok] = durations_old
+        if self.graph:
+            run = self._cached_graph(
+                ("retime", 1, xb, trb, tyb, durations_old is not None),
+                lambda: self.model.capture_retime_bucketed(
+                    xb, trb, tyb, stft=stft, given_durations=durations_old is not None))
+            neutral = given is None and scale is None and target == 0 and float(rate) == 1.0
+            ctl = None if neutral else [dict(given=g_row, tok_scale=s_row, rate=float(rate),
+                                             target=target)]
+            o, y_len, dur_old, dur_new, meta, scores = run(
+                x, lens, [src], [tgt], x=xt, x_lengths=[n_tok] if xb else None, emo=e,
+                controls=ctl, noise=noise, durations_old=d_row)
+        else:
+            pad = self._pad_rows
+            ctl = dict(given=torch.from_numpy(g_row).view(1, -1).to(dev),
+                       tok_scale=torch.from_numpy(s_row).view(1, -1).to(dev),
+                       rate=torch.full((1,), float(rate), device=dev),
+                       target=pad([target], 1, dtype=i32))
+            o, y_len, dur_old, dur_new, meta, scores = self.model.retime_bucketed(
+                pad(x, 1, trb * hop + hop - 1), pad(lens, 1, dtype=i32),
+                pad([src], 1, dtype=torch.long), pad([tgt], 1, dtype=torch.long), noise, trb, tyb,
+                stft=stft, x=None if xt is None else pad(xt, 1, xb),
+                x_lengths=pad([n_tok], 1, dtype=i32) if xb else None, emo=e,
+                durations_old=None if d_row is None else torch.from_numpy(d_row).view(1, -1).to(dev),
+                controls=ctl)
+        posted = None if post is None else post(o[:, 0], y_len, hop)
+        parts = [meta[:, 0], dur_old[0, :nt], dur_new[0, :nt]]
+        if scores is not None:
+            parts.append(scores[0, :nt].view(i32))
+        host = self._to_host(torch.cat(parts))  # the one copy back (synchronises)
+        y_new, w_st, p_st = (int(v) for v in host[:3])
+        if p_st:
+            raise ValueError(
+                f"target_frames={target_frames!r} cannot be met (the pins leave no room for it), "
+                f"or the old durations do not sum to the recording's {frames} frames")
+        if w_st:
+            raise ValueError(f"the retimed recording of {y_new} frames does not fit its bucket "
+                             f"of {tyb} frames")
+        d_old, d_new = host[3:3 + nt].copy(), host[3 + nt:3 + 2 * nt].copy()
+        sc = host[3 + 2 * nt:].view(np.float32).copy() if scores is not None else None
+        return (o[:, 0] if post is None else posted), y_new, d_old, d_new, sc
+
+    def retime(self, wav, spkid_src, spkid_tgt, *, speed=1.0, target_frames=None, text=None,
+               emo=None, durations=None, token_scale=None, durations_old=None,
+               sampling_rate_in=None, noise_scale=0.0, graph=True, return_durations=False):
+        """Retime a recording and keep its performance and voice: ``wav`` (as
+        ``convert`` takes it) of speaker spkid_src comes back in the voice of
+        spkid_tgt (the same id: its own) with its timing changed in latent
+        space (SynthesizerTrn.retime).  ``speed`` multiplies
+        every duration, as duration_rate does in ``infer`` (1.1: ten per cent
+        slower); ``target_frames``: the result lasts exactly that many model
+        frames (speed is then not applied).  With ``text`` [N, c] (and ``emo``
+        as ``align`` takes it) the recording is aligned with it, or
+        ``durations_old`` (N frame counts summing to the recording's frames)
+        taken as its alignment, and each token can be timed on its own:
+        ``durations`` (N frame counts, < 0: free) pins tokens, ``token_scale``
+        (N factors) multiplies the free ones.  Without text the take is one
+        token.  noise_scale as in ``convert``.  ``graph=False`` runs the same
+        chain eagerly and gives the same bytes.
+
+        Returns wav float32 [y_new * hop] at the model's rate; with
+        ``return_durations`` (wav, dur_old int32 [N], dur_new int32 [N],
+        scores float32 [N] of the alignment or None).  Raises ValueError,
+        before anything is uploaded, for a recording of more than 4096 frames
+        or of fewer frames than tokens, a speed or token_scale outside [1/16,
+        16] or not finite, durations or token_scale without text, lengths
+        that do not match the text, durations_old that do not sum to the
+        frames, a result that may exceed 4096 frames; after the copy for a
+        target the pins leave no room for."""
+        keep, self.graph = self.graph, bool(graph) and self.graph
+        try:
+            w, y_new, d_old, d_new, sc = self._retime_rows(
+                wav, spkid_src, spkid_tgt, speed, 1.0, target_frames, text, emo, durations,
+                token_scale, durations_old, sampling_rate_in, noise_scale)
+        finally:
+            self.graph = keep
+        out = w[0, :y_new * self.hop_size].cpu().numpy()
+        return (out, d_old, d_new, sc) if return_durations else out
+
+    def retime_pcm(self, wav, spkid_src, spkid_tgt, *, speed=1.0, target_frames=None, text=None,
+                   emo=None, durations=None, token_scale=None, durations_old=None,
+                   sampling_rate_in=None, noise_scale=0.0, graph=True, return_durations=False,
+                   pitch=1.0, sampling_rate=None, volume=1.0, tail_silence=0.0):
+        """retime plus convert_pcm's output stage on the device, the length
+        read on the device.  The durations' rate is speed / pitch, so the
+        change of length of the pitch resampler cancels, as in ``speaking``:
+        pitch changes and the length stays.  ``target_frames`` counts model
+        frames before the output stage.  Returns (pcm int16 [n],
+        n_model_samples), with ``return_durations`` followed by (dur_old,
+        dur_new, scores)."""
+        out = self._output(pitch, sampling_rate, volume, tail_silence)
+        keep, self.graph = self.graph, bool(graph) and self.graph
+        try:
+            pcm, y_new, d_old, d_new, sc = self._retime_rows(
+                wav, spkid_src, spkid_tgt, speed, pitch, target_frames, text, emo,
+                durations, token_scale, durations_old, sampling_rate_in, noise_scale,
+                post=lambda w, lengths, scale: self._post(w, out, lengths=lengths,
+                                                          length_scale=scale))
+        finally:
+            self.graph = keep
+        n = y_new * self.hop_size
+        res = (pcm[0, :self._n_out(n, out.passes) + out.tail].cpu().numpy(), n)
+        return res + (d_old, d_new, sc) if return_durations else res
+
     # -- forced alignment of long recordings: many segments, any length (DESIGN.md 4u)
     # the caps of align_long: the total tokens of a text (a 40-minute reading
     # at 1 token per 6 frames), and the bytes of the search's workspace plus

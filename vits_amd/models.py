@@ -1748,6 +1748,282 @@ class SynthesizerTrn(nn.Module):
         return self._graph_run(run, graph, static, t_x_old=t_x_old, t_x_new=t_x_new, t_rec=t_rec,
                                t_y=t_y, batch=batch, replay=replay)
 
+    # ---------------------------------------------------- retiming a recording
+    def _retime_tail(self, z, lens, g_tgt):
+        """Reverse flow (in place on z), decoder and the cut at y_new * hop."""
+        engine.get_plan(self.flow, engine.CouplingFlowPlan).run_(z, g_tgt, lengths=lens[0])
+        o = engine.get_plan(self.dec, engine.GeneratorPlan).run(z, g_tgt, lengths=lens[1:])
+        out = torch.empty_like(o)  # (the cut of _vc_core)
+        engine.ops.resample_poly(o[:, 0], 1, 1, lengths=lens[0], length_scale=self.hop_total,
+                                 out=out[:, 0])
+        return out
+
+    @staticmethod
+    def _retime_sources(dur_old, dur_new, ty):
+        """The warp rule of vits_retime_warp on the host, in int64 tensors:
+        (j0, j1 int64 [y_new], w fp32 [y_new], plain bool [y_new]); ``plain``
+        frames copy z[j0]."""
+        do = dur_old.to(torch.int64).clamp(0, 1 << 18)
+        dn = dur_new.to(torch.int64).clamp(0, 1 << 18)
+        c_old = torch.cumsum(do, 0) - do
+        c_new = torch.cumsum(dn, 0) - dn
+        i = torch.repeat_interleave(torch.arange(do.numel()), dn)  # each frame's owner
+        k = torch.arange(i.numel(), dtype=torch.int64) - c_new[i]
+        num = (2 * k + 1) * do[i] - dn[i]
+        den = 2 * dn[i]
+        qf = torch.div(num, den, rounding_mode="floor")
+        r = num - qf * den
+        j0 = (c_old[i] + qf).clamp(0, ty - 1)
+        j1 = (c_old[i] + qf + 1).clamp(0, ty - 1)
+        w = r.to(torch.float32) / den.to(torch.float32)  # (IEEE division on the host)
+        return j0, j1, w, (r == 0) | (j0 == j1)
+
+    @torch.no_grad()
+    def retime(self, y, y_lengths, sid_src, sid_tgt, dur_old, dur_new, noise=None):
+        """Retime a recording in latent space.  y [1, F, Ty] is the linear
+        spectrogram of speaker sid_src; ``dur_old`` (Tx ints summing to Ty)
+        says how many frames each token (any unit of the take: one for the
+        whole of it) lasts, ``dur_new`` how many it shall last.  Eager, B = 1,
+        exact lengths: the definition retime_bucketed is held to.
+
+        z_p = flow(enc_q(y); g_src) is _audio_latents' (``noise`` [1, C, Ty]
+        pre-scaled, None: the posterior mean).  With c_old / c_new the
+        exclusive prefix sums of the durations, frame t of the result, the
+        k-th of token i, reads the recording at c_old[i] + (k + 1/2) *
+        dur_old[i] / dur_new[i] - 1/2, between its two nearest frames (clamped
+        to the recording), linearly: vits_retime_warp's rule (include/
+        vits_amd.h), here with torch indexing and the same separately rounded
+        fp32 subtraction, product and sum.  Then z_hat = flow^-1(z_warp;
+        g_tgt), o = dec(z_hat; g_tgt), masked at y_new = sum(dur_new).
+
+        Returns (o [1, 1, y_new * hop] in y's dtype, (z_p, z_warp, z_hat)).
+        With dur_new == dur_old the warp copies and o is bit for bit
+        voice_conversion(y, ., sid_src, sid_tgt); samples further than
+        edit_context_frames() frames from every retimed token are that too,
+        shifted by the change of length before them."""
+        engine._check_gpu(y, "SynthesizerTrn.retime")
+        if y.size(0) != 1:
+            raise ValueError("retime: one recording per call (retime_bucketed takes batches)")
+        dev = y.device
+        i32 = torch.int32
+        Ty = int(y_lengths.reshape(-1)[0])
+        do = torch.as_tensor(dur_old).reshape(-1).cpu().to(torch.int64)
+        dn = torch.as_tensor(dur_new).reshape(-1).cpu().to(torch.int64)
+        if do.numel() != dn.numel() or do.numel() == 0:
+            raise ValueError(f"retime: {do.numel()} old durations against {dn.numel()} new ones")
+        if int(do.min()) < 0 or int(dn.min()) < 0 or int(do.sum()) != Ty or Ty < 1:
+            raise ValueError(f"retime: dur_old must be >= 0 and sum to the recording's {Ty} frames")
+        y_new = int(dn.sum())
+        if y_new < 1:
+            raise ValueError("retime: the new durations leave no frame")
+        y_len = torch.full((1,), Ty, device=dev, dtype=i32)
+        spec = engine._f32(y)[:, :, :Ty].contiguous()
+        g_tgt = engine._f32(self.emb_g(sid_tgt))
+        _, z_p, _ = self._audio_latents(spec, noise, y_len, engine._f32(self.emb_g(sid_src)))
+        j0, j1, w, plain = (t.to(dev) for t in self._retime_sources(do, dn, Ty))
+        a = z_p[:, :, j0]
+        d = z_p[:, :, j1] - a
+        p = w * d
+        z_warp = torch.where(plain, a, a + p).contiguous()
+        lens = torch.tensor([[y_new * m] for m in self._stage_mult()], dtype=i32).to(dev)
+        z_hat = z_warp.clone()
+        o = self._retime_tail(z_hat, lens, g_tgt)
+        return (o[:, :, :y_new * self.hop_total].to(y.dtype),
+                tuple(t.to(y.dtype) for t in (z_p, z_warp, z_hat)))
+
+    @torch.no_grad()
+    def retime_bucketed(self, wav, n_samples, sid_src, sid_tgt, noise, t_rec, t_y, *, stft, x=None,
+                        x_lengths=None, emo=None, durations_old=None, controls=None):
+        """``retime`` from the waveform with NO host synchronisation, over
+        static buckets of t_rec recording frames and t_y output frames
+        (capture_retime_bucketed makes it one hipGraph).  wav [B, >= t_rec *
+        hop] fp32 and n_samples int32 [B] as convert_bucketed takes them
+        (``stft`` too); noise [B, C, t_rec] (pre-scaled posterior draw) or
+        None.  The durations to warp from:
+          - ``x`` [B, t_x, c] with ``x_lengths`` int32 [B] and ``emo``: the
+            recording is aligned with its text (text encoder, neg_cent, MAS);
+          - ``durations_old`` int32 [B, t_x] with ``x_lengths``: those three
+            steps are skipped (x and emo are not read);
+          - neither: the row is one token of y_len frames; no text encoder
+            and no MAS run.
+        ``controls`` = None or dict(given= int32 [B, t_x], tok_scale= fp32 [B,
+        t_x], rate= fp32 [B], target= int32 [B]), ops.retime_plan's.
+
+        The chain: ragged STFT -> _audio_latents -> dur_old -> retime_plan ->
+        retime_warp -> reverse flow -> decoder -> cut, under
+        ops.length_skip(64).  Returns (o fp32 [B, 1, t_y * hop], y_new int32
+        [B], dur_old int32 [B, t_x], dur_new int32 [B, t_x], meta int32 [3, B]
+        = the plan's total | warp status | plan status, scores fp32 [B, t_x]
+        or None): where both statuses are 0, the first y_new * hop samples of
+        row b are bit for bit ``retime`` of that row alone under these
+        durations; a row whose warp status is -1 is zero with y_new 0."""
+        engine._check_gpu(wav, "SynthesizerTrn.retime_bucketed")
+        t_rec, t_y = int(t_rec), int(t_y)
+        dev = wav.device
+        B = wav.shape[0]
+        controls = dict(controls or {})
+        unknown = set(controls) - {"given", "tok_scale", "rate", "target"}
+        if unknown:
+            raise ValueError(f"retime_bucketed: unknown control(s) {sorted(unknown)}")
+        if durations_old is not None and x_lengths is None:
+            raise ValueError("retime_bucketed: durations_old need x_lengths")
+        if durations_old is None and x is not None and (x_lengths is None or emo is None):
+            raise ValueError("retime_bucketed: a text needs x_lengths and emo")
+        spec, y_len = self._spec_rows("retime_bucketed", wav, n_samples, t_rec, stft)
+        scores = x_len = None
+        if x_lengths is not None:
+            x_len = x_lengths.to(device=dev, dtype=torch.int32).contiguous()
+        with engine.ops.length_skip(64):
+            if durations_old is None and x is not None:
+                dur_old, scores, (z_p, _, _, _) = self._align_core(spec, noise, y_len, x, x_len,
+                                                                   emo, sid_src)
+            else:
+                dur_old = y_len.view(B, 1) if durations_old is None else durations_old
+                if durations_old is None:
+                    x_len = None
+                _, z_p, _ = self._audio_latents(spec, noise, y_len,
+                                                engine._f32(self.emb_g(sid_src)))
+            dur_new, total, pstat = engine.ops.retime_plan(
+                dur_old, y_len, x_len=x_len, given=controls.get("given"),
+                tok_scale=controls.get("tok_scale"), rate=controls.get("rate"),
+                target=controls.get("target"))
+            z, lens, wmeta = engine.ops.retime_warp(z_p.contiguous(), dur_old, dur_new, y_len, t_y,
+                                                    x_len=x_len, stage_mult=self._stage_mult())
+            o = self._retime_tail(z, lens, engine._f32(self.emb_g(sid_tgt)))
+        meta = torch.cat([wmeta, pstat.reshape(1, B)], dim=0)
+        return o, lens[0], dur_old, dur_new, meta, scores
+
+    @torch.no_grad()
+    def capture_retime_bucketed(self, t_x, t_rec, t_y, batch=1, warmup=2, *, stft,
+                                given_durations=False):
+        """One hipGraph for retime_bucketed over [batch, t_x tokens, t_rec
+        recording frames, t_y output frames] (``stft`` as there).  t_x == 0
+        captures the text-free chain (one token per row); ``given_durations``:
+        the graph reads durations_old from a static buffer and holds no
+        alignment.  Returns run(wav, n_samples, sid_src, sid_tgt, x=None,
+        x_lengths=None, emo=None, controls=None, noise=None,
+        durations_old=None) -> retime_bucketed's outputs as views of static
+        buffers.  wav [n, <= t_rec * hop + hop - 1] fp32 rows, the lengths
+        and speakers host ints (or tensors), x [n, <= t_x, c], emo [n, 1024],
+        ``controls`` a list of n dicts(given=, tok_scale=, rate=, target=) or
+        None: the static given / tok_scale / rate / target are then reset to
+        neutral on the device (nothing is uploaded), noise [n, C, t_rec] or
+        None (the static noise is zeroed), durations_old [n, <= t_x] ints.
+        Rows at or past n have no samples: warp status -1."""
+        dev = next(self.parameters()).device
+        dt = next(self.parameters()).dtype
+        n_fft, hop, win = (int(v) for v in stft)
+        t_x, t_rec, t_y, batch = (int(v) for v in (t_x, t_rec, t_y, batch))
+        if given_durations and t_x < 1:
+            raise ValueError("capture_retime_bucketed: given durations need t_x >= 1")
+        text = t_x > 0 and not given_durations
+        tw = max(t_x, 1)  # (a text-free row is one token)
+        cap = t_rec * hop + hop - 1
+        i32 = torch.int32
+        static = dict(wav=torch.zeros(batch, cap, device=dev),
+                      n=torch.zeros(batch, device=dev, dtype=i32),
+                      src=torch.zeros(batch, device=dev, dtype=torch.long),
+                      tgt=torch.zeros(batch, device=dev, dtype=torch.long),
+                      given=torch.full((batch, tw), -1, device=dev, dtype=i32),
+                      tok_scale=torch.ones(batch, tw, device=dev),
+                      rate=torch.ones(batch, device=dev),
+                      target=torch.zeros(batch, device=dev, dtype=i32),
+                      noise=torch.zeros(batch, self.inter_channels, t_rec, device=dev))
+        if t_x > 0:
+            static["xl"] = torch.zeros(batch, device=dev, dtype=i32)
+        if text:
+            static["x"] = torch.zeros(batch, t_x, self.text_channels, device=dev, dtype=dt)
+            static["emo"] = torch.zeros(batch, 1024, device=dev, dtype=dt)
+        if given_durations:
+            static["dur_old"] = torch.zeros(batch, t_x, device=dev, dtype=i32)
+        self._vc_window(win, dev)  # (built outside the capture)
+        ctl = {k: static[k] for k in ("given", "tok_scale", "rate", "target")}
+        state = dict(neutral=True)
+
+        def body():
+            return self.retime_bucketed(
+                static["wav"], static["n"], static["src"], static["tgt"], static["noise"], t_rec,
+                t_y, stft=(n_fft, hop, win), x=static.get("x"), x_lengths=static.get("xl"),
+                emo=static.get("emo"), durations_old=static.get("dur_old"), controls=ctl)
+
+        graph, out = self._capture_body(body, warmup, dev)
+        _ints = self._row_ints
+
+        def replay():
+            graph.replay()
+            return out
+
+        def fill_controls(controls, n):
+            if not any(v is not None for row in controls or () for v in (row or {}).values()):
+                if not state["neutral"]:  # reset on the device, nothing uploaded
+                    static["given"].fill_(-1)
+                    static["tok_scale"].fill_(1.0)
+                    static["rate"].fill_(1.0)
+                    static["target"].zero_()
+                    state["neutral"] = True
+                return
+            state["neutral"] = False
+            given = torch.full((batch, tw), -1, dtype=i32)
+            scale = torch.ones(batch, tw)
+            rate = torch.ones(batch)
+            target = torch.zeros(batch, dtype=i32)
+            for i, row in enumerate(controls):
+                row = row or {}
+                unknown = set(row) - set(ctl)
+                if unknown or i >= n:
+                    raise ValueError(f"retime replay: controls {sorted(unknown)} of row {i}")
+                for name, buf in (("given", given), ("tok_scale", scale)):
+                    if row.get(name) is not None:
+                        v = torch.as_tensor(row[name], dtype=buf.dtype).reshape(-1).cpu()
+                        if v.numel() > tw:
+                            raise ValueError(f"retime replay: {v.numel()} values of {name} do "
+                                             f"not fit {tw} tokens")
+                        buf[i, :v.numel()] = v
+                if row.get("rate") is not None:
+                    rate[i] = float(row["rate"])
+                if row.get("target") is not None:
+                    target[i] = int(row["target"])
+            for k, v in (("given", given), ("tok_scale", scale), ("rate", rate),
+                         ("target", target)):
+                static[k].copy_(v)
+
+        def run(wav, n_samples, sid_src, sid_tgt, x=None, x_lengths=None, emo=None, controls=None,
+                noise=None, durations_old=None):
+            n = wav.shape[0]
+            if not 1 <= n <= batch or wav.shape[1] > cap:
+                raise ValueError(f"retime replay: wav {tuple(wav.shape)} does not fit "
+                                 f"[{batch}, {cap}]")
+            if text != (x is not None) or given_durations != (durations_old is not None):
+                raise ValueError("retime replay: a text goes with a graph captured with t_x > 0, "
+                                 "durations_old with one captured with given_durations, and "
+                                 "only with it")
+            if text and (x.shape[0] != n or x.shape[1] > t_x):
+                raise ValueError(f"retime replay: x {tuple(x.shape)} does not fit [{n}, {t_x}, c]")
+            fill_controls(controls, n)
+            static["wav"].zero_()
+            static["wav"][:n, :wav.shape[1]].copy_(wav)
+            _fill_rows(static["n"], _ints(n_samples, n, i32), n)
+            _fill_rows(static["src"], _ints(sid_src, n, torch.long), n)
+            _fill_rows(static["tgt"], _ints(sid_tgt, n, torch.long), n)
+            if t_x > 0:
+                _fill_rows(static["xl"], _ints(x_lengths, n, i32), n)
+            if text:
+                _fill_rows(static["x"], x, n, x.shape[1])
+                _fill_rows(static["emo"], emo, n)
+            if given_durations:
+                d = torch.as_tensor(durations_old, dtype=i32).reshape(n, -1)
+                if d.shape[1] > t_x:
+                    raise ValueError(f"retime replay: {d.shape[1]} durations_old do not fit "
+                                     f"{t_x} tokens")
+                _fill_rows(static["dur_old"], d, n, d.shape[1])
+            static["noise"].zero_()
+            if noise is not None:
+                static["noise"][:n].copy_(noise)
+            return replay()
+
+        return self._graph_run(run, graph, static, t_x=t_x, t_rec=t_rec, t_y=t_y, batch=batch,
+                               replay=replay)
+
     # --------------------------------------- the two halves, captured apart
     @torch.no_grad()
     def capture_infer_p1(self, t_x, warmup=2):

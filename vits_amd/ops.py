@@ -2472,3 +2472,102 @@ def edit_patch(orig: torch.Tensor, o: torch.Tensor, y_len_old: torch.Tensor,
         out.data_ptr(), out.stride(0), out.shape[1], out_len.data_ptr(), B,
         _stream_ptr(o.device)), "vits_edit_patch")
     return out, out_len
+
+
+# ---------------------------------------------------------------------------
+# retiming a recording (retime.hip)
+# ---------------------------------------------------------------------------
+
+
+def _dur_rows(what: str, t, B, t_x, name: str):
+    """An int32 [B, t_x] device tensor whose rows are contiguous (B / t_x None:
+    taken from the tensor)."""
+    if (not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.int32
+            or t.stride(1) != 1 or t.stride(0) < t.shape[1]
+            or (B is not None and tuple(t.shape) != (B, t_x))):
+        shape = "[B, t_x]" if B is None else f"[{B}, {t_x}]"
+        raise _lib.VitsAmdError(f"{what}: {name} must be an int32 {shape} tensor with contiguous "
+                                "rows")
+    require_device(t)
+    return t
+
+
+def retime_plan(dur_old: torch.Tensor, y_len_old: torch.Tensor, *,
+                x_len: Optional[torch.Tensor] = None, given: Optional[torch.Tensor] = None,
+                tok_scale: Optional[torch.Tensor] = None, rate: Optional[torch.Tensor] = None,
+                target: Optional[torch.Tensor] = None, dur: Optional[torch.Tensor] = None,
+                meta: Optional[torch.Tensor] = None):
+    """A recording's new per-token durations from its old ones, on the device
+    with no host sync (vits_retime_plan, include/vits_amd.h has the rule).
+    ``dur_old`` int32 [B, t_x] (rows may be strided), ``y_len_old`` / ``x_len``
+    int32 [B]; ``given`` int32 [B, t_x]: >= 0 pins a token to that many frames,
+    < 0 leaves it free; ``tok_scale`` fp32 [B, t_x] and ``rate`` fp32 [B]
+    multiply the free tokens' durations; ``target`` int32 [B]: > 0 = the row
+    lasts exactly that many frames (``rate`` is then not applied).  Returns
+    (dur_new int32 [B, t_x], total int32 [B], status int32 [B]); status 1: the
+    row is inconsistent or its target cannot be met, and it keeps dur_old.
+    With no control dur_new == dur_old."""
+    what = "retime_plan"
+    dur_old = _dur_rows(what, dur_old, None, None, "dur_old")
+    B, t_x = dur_old.shape
+    i32 = torch.int32
+    y_len_old = _edit_arg(what, y_len_old, i32, (B,), "y_len_old")
+    x_len = _edit_arg(what, x_len, i32, (B,), "x_len", True)
+    given = _edit_arg(what, given, i32, (B, t_x), "given", True)
+    tok_scale = _edit_arg(what, tok_scale, torch.float32, (B, t_x), "tok_scale", True)
+    rate = _edit_arg(what, rate, torch.float32, (B,), "rate", True)
+    target = _edit_arg(what, target, i32, (B,), "target", True)
+    dev = dur_old.device
+    if dur is None:
+        dur = torch.empty(B, t_x, device=dev, dtype=i32)
+    if meta is None:
+        meta = torch.empty(2, B, device=dev, dtype=i32)
+    _edit_arg(what, dur, i32, (B, t_x), "dur")
+    _edit_arg(what, meta, i32, (2, B), "meta")
+    check(_lib.load().vits_retime_plan(
+        dur_old.data_ptr(), dur_old.stride(0), _ptr(x_len), t_x, y_len_old.data_ptr(),
+        _ptr(given), _ptr(tok_scale), _ptr(rate), _ptr(target), dur.data_ptr(), meta.data_ptr(),
+        B, _stream_ptr(dev)), "vits_retime_plan")
+    return dur, meta[0], meta[1]
+
+
+def retime_warp(z_p_rec: torch.Tensor, dur_old: torch.Tensor, dur_new: torch.Tensor,
+                y_len_old: torch.Tensor, t_y: int, *, x_len: Optional[torch.Tensor] = None,
+                stage_mult=(1,), out: Optional[torch.Tensor] = None):
+    """The recording's latents ``z_p_rec`` fp32 [B, C, t_rec] resampled along
+    time so that token x lasts dur_new[x] frames instead of dur_old[x]
+    (vits_retime_warp: the centre-aligned piecewise-linear map of each token's
+    new frames onto its old ones; the exact copy where the two agree).
+    ``dur_old`` / ``dur_new`` int32 [B, t_x] (rows may be strided), ``t_y`` the
+    output bucket.  Returns (z fp32 [B, C, t_y], zero past y_new, lens int32
+    [n_stage, B] = y_new * stage_mult, meta int32 [2, B] = y_new | status);
+    status -1: y_new > t_y or no recording; the row is then zero with length
+    0 and y_new is still reported."""
+    what = "retime_warp"
+    if (not isinstance(z_p_rec, torch.Tensor) or z_p_rec.dim() != 3
+            or z_p_rec.dtype != torch.float32 or not z_p_rec.is_contiguous()):
+        raise _lib.VitsAmdError(f"{what}: z_p_rec must be a contiguous fp32 [B, C, t_rec] tensor")
+    require_device(z_p_rec)
+    B, C_, t_rec = z_p_rec.shape
+    dur_old = _dur_rows(what, dur_old, None, None, "dur_old")
+    if dur_old.shape[0] != B:
+        raise _lib.VitsAmdError(f"{what}: dur_old has {dur_old.shape[0]} rows, z_p_rec {B}")
+    t_x = dur_old.shape[1]
+    dur_new = _dur_rows(what, dur_new, B, t_x, "dur_new")
+    i32 = torch.int32
+    y_len_old = _edit_arg(what, y_len_old, i32, (B,), "y_len_old")
+    x_len = _edit_arg(what, x_len, i32, (B,), "x_len", True)
+    t_y = int(t_y)
+    dev = z_p_rec.device
+    if out is None:
+        out = torch.empty(B, C_, t_y, device=dev, dtype=torch.float32)
+    _edit_arg(what, out, torch.float32, (B, C_, t_y), "out")
+    n_stage = len(stage_mult)
+    lens = torch.empty(n_stage, B, device=dev, dtype=i32)
+    meta = torch.empty(2, B, device=dev, dtype=i32)
+    mult = (C.c_int32 * n_stage)(*[int(v) for v in stage_mult])
+    check(_lib.load().vits_retime_warp(
+        z_p_rec.data_ptr(), t_rec, dur_old.data_ptr(), dur_old.stride(0), dur_new.data_ptr(),
+        dur_new.stride(0), _ptr(x_len), t_x, y_len_old.data_ptr(), out.data_ptr(), B, C_, t_y,
+        lens.data_ptr(), mult, n_stage, meta.data_ptr(), _stream_ptr(dev)), "vits_retime_warp")
+    return out, lens, meta

@@ -335,6 +335,79 @@ class VITSWrap(object):
         return out
 
     @torch.no_grad()
+    def retiming(self, inputs: dict) -> dict:
+        """Retiming request: the fields of ``converting`` ("spkid_tgt"
+        defaults to "spkid_src": the take keeps its voice) plus "speed" (1.1:
+        ten per cent slower; clamped to 0.5 .. 2 as in ``speaking``),
+        "duration_s" (the result lasts round(s * rate / hop) model frames;
+        speed is then not applied), and optionally "text" (what the recording
+        says, one segment) with "emotion", and with it "durations" (frames
+        per token of the front end's vector sequence, < 0: free) and
+        "token_scale" (a factor per token).  Pitch changes and the length
+        stays: the durations' rate is speed / pitch.  -> the dict of
+        ``converting`` plus "length_s" (the result's seconds at the model's
+        rate, before pitch and rate changes) and, with text, "durations_old"
+        (int32 [Tx], the recording's alignment), "durations" (int32 [Tx], the
+        frames per token of the result) and "boundaries_s" (of the result).
+        Needs device_post=True on a ROCm GPU (EmoVITS.retime_pcm); recordings
+        of at most 4096 frames."""
+        if not self.device_post:
+            raise ValueError("VITSWrap.retiming needs device_post=True on a ROCm GPU")
+        if "wav" not in inputs or "spkid_src" not in inputs:
+            raise ValueError("retiming needs the recording (wav) and its speaker (spkid_src)")
+        volume = max(0.0, min(1.0, float(inputs.get("volume", self.default_volume))))
+        speed = max(0.5, min(2.0, float(inputs.get("speed", self.default_speed))))
+        pitch = max(0.5, min(2.0, float(inputs.get("pitch", self.default_pitch))))
+        sampling_rate = min(48000, max(8000, int(inputs.get("sampling_rate",
+                                                            self.default_sampling_rate))))
+        tail_silence = float(inputs.get("tail_silence", self.default_tail_silece))
+        utt_id = inputs.setdefault("id", str(time.time()).replace(".", "_"))
+        sp = self.speecher
+        text = inputs.get("text")
+        if text is None and (inputs.get("durations") is not None
+                             or inputs.get("token_scale") is not None):
+            raise ValueError("retiming: durations and token_scale are per token: they need text")
+        target = None
+        if inputs.get("duration_s") is not None:
+            sec = float(inputs["duration_s"])
+            if not np.isfinite(sec) or sec <= 0:
+                raise ValueError(f"retiming: duration_s must be a positive number, got {sec}")
+            target = int(round(sec * sp.sampling_rate / sp.hop_size))
+            if target < 1:
+                raise ValueError(f"retiming: duration_s = {sec} is less than one frame")
+        vec = None
+        t0 = time.time()
+        if text is not None:
+            ids, texts = self._split_utt_text(utt_id, text)
+            if len(texts) != 1:
+                raise ValueError(f"retiming: the text splits into {len(texts)} segments of at "
+                                 f"most {self.max_utt_length} characters; one segment per "
+                                 "recording")
+            _, _, vec = self.textparser(ids[0], texts[0])
+        t1 = time.time()
+        spkid_src = int(inputs["spkid_src"])
+        pcm, n_model, d_old, d_new, _ = sp.retime_pcm(
+            inputs["wav"], spkid_src, int(inputs.get("spkid_tgt", spkid_src)), speed=speed,
+            target_frames=target, text=vec, emo=inputs.get("emotion"),
+            durations=inputs.get("durations"), token_scale=inputs.get("token_scale"),
+            sampling_rate_in=inputs.get("sampling_rate_in"), pitch=pitch,
+            sampling_rate=sampling_rate, volume=volume, tail_silence=tail_silence,
+            return_durations=True)
+        t_back = time.time() - t1
+        out = inputs
+        out["wav"] = _gen_wav_header(len(pcm), sampling_rate, 16) + pcm.tobytes()
+        out["sr"] = sampling_rate
+        out["segment_info"] = [{"start_ms": 0.0, "end_ms": len(pcm) / sampling_rate * 1000}]
+        out["time_used_frontend"] = (t1 - t0) * 1000
+        out["time_used_backend"] = t_back * 1000
+        out["rtf"] = t_back / max(1e-9, n_model / self.default_sampling_rate)
+        out["length_s"] = n_model / sp.sampling_rate
+        if text is not None:
+            out["durations_old"] = d_old
+            self._with_durations(out, d_new)
+        return out
+
+    @torch.no_grad()
     def speaking_like(self, inputs: dict) -> dict:
         """``text`` in the voice of ``spkid`` with the timing of a recording:
         {"wav", "sampling_rate_in", "spkid_src", "text"} as ``aligning`` takes
